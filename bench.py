@@ -3,7 +3,15 @@
 (BASELINE.json metric; configs[2] at N=1: batch 256 on one MI355X; configs[3] at N=8:
 batch 2048 = 8 x 256, weak scaling, RCCL all-gather of logits).
 
-python bench.py --gpus N --steps K --warmup W
+python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: set up, W warm-up steps, K timed steps,
+one JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step and the run's
+configuration). --dump-outputs DIR writes what the last timed step returned to its caller (the
+gathered logits, DIR/logits.npy, float32); the weights and inputs are seeded, so two builds run with
+the same arguments can be compared output for output. --full adds everything else described below:
+the eager roofline regions, the committed PMC traffic, the per-launch table (--layers) and the CPU
+baseline.
 
 N > 1: one process per GPU. Under torch.distributed.run (WORLD_SIZE set) this process is one
 rank; started directly with --gpus N it launches `python -m torch.distributed.run
@@ -16,14 +24,14 @@ calibrates the static ranges on batch 0, as a real evaluation calibrates on its 
 the timed steps cycle through all of them. Ranks calibrate together (engine.set_dp_group: the
 per-layer maxima are MAX-all-reduced), so the gathered logits equal a single-GPU forward of the
 global batch bit for bit. Prints ONE
-JSON line on rank 0 with the roofline of the dominant kernel family (the quantized conv:
+JSON line on rank 0, with --full including the roofline of the dominant kernel family (the quantized conv:
 qconv_glds_kernel and the fused stem + pool, every launch incl. the stem) and the CPU baseline (the
 reference's fp32 torch-CPU forward restated in oracle/torch_ref.py, timed on a bounded sample).
 
 Timing: `value` comes from the production path, the static-range forward replayed from a
 captured HIP graph. HIP events recorded inside a graph capture cannot be timed on ROCm 7.2
 (elapsed_time -> hipErrorInvalidHandle, tools/probe_graph_events.py), so the per-launch
-kernel durations come from a second region run right after the timed one: the same forward
+kernel durations come from a second region (--full) run right after the timed one: the same forward
 launched eagerly (the same kernels the graph replays) with HIP events around every conv
 launch on the stream it is launched on, one launch at a time (the graph runs each stage's
 downsample conv on a side stream beside conv1/conv2; the roofline region runs it serially so
@@ -227,16 +235,26 @@ def main():
     ap.add_argument("--config", default="r50_mixed", choices=sorted(CONFIGS))
     ap.add_argument("--limbs", type=int, default=3,
                     help="activation int8 limbs: 3 = int24 codes (parity mode, default), 2 = int16 (fast mode)")
-    ap.add_argument("--roofline-steps", type=int, default=3, help="eager steps timed per launch for the roofline")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--layers", action="store_true", help="print a per-launch roofline table (stderr)")
-    ap.add_argument("--cpu-iters", type=int, default=2, help="timed CPU-baseline iterations (after 1 warm-up)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (the gathered logits) to DIR/logits.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the eager roofline regions, attach the PMC traffic and time the CPU baseline")
+    ap.add_argument("--roofline-steps", type=int, default=3,
+                    help="--full: eager steps timed per launch for the roofline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave the CPU baseline out")
+    ap.add_argument("--layers", action="store_true", help="--full: print a per-launch roofline table (stderr)")
+    ap.add_argument("--cpu-iters", type=int, default=2,
+                    help="--full: timed CPU-baseline iterations (after 1 warm-up)")
     ap.add_argument("--chunk", type=int, default=None, help="images per pass (Infinity-Cache blocking)")
     ap.add_argument("--streams", type=int, default=None,
                     help="batch slices run concurrently on their own streams (default: engine.STREAMS)")
     ap.add_argument("--batches", type=int, default=4,
                     help="distinct device-resident global batches cycled through the timed steps")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.layers and not args.full:
+        ap.error("--layers prints the roofline table of the --full run: add --full")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # one process per GPU: relaunch under torch.distributed.run as a CHILD (no exec), before
@@ -320,7 +338,7 @@ def main():
     t0 = time.perf_counter()
     for e0, e1 in evs:
         e0.record()
-        step()
+        last = step()
         e1.record()
     torch.cuda.synchronize()
     t1 = time.perf_counter()
@@ -333,6 +351,60 @@ def main():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed to its caller: the [global batch, 1000] logits (~1 MB at
+        # the default batch), read before anything else runs on the device
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "logits.npy"), last.detach().float().cpu().numpy())
+    images = args.batch * world * args.steps
+    value = images / elapsed
+    ms_per_step = elapsed / args.steps * 1e3
+
+    def result(roof):
+        config = {"workload": desc, "assignment": assign, "batch_per_gpu": args.batch,
+                  "global_batch": args.batch * world, "act_limbs": args.limbs,
+                  "act_code": {1: "int8", 2: "int16 (2 int8 limbs)", 3: "int24 (3 int8 limbs)"}[args.limbs],
+                  "parallelism": "dp%d" % world,
+                  "range_mode": engine.get_range_mode(), "chunk": engine.CHUNK[0],
+                  "hip_graph": bool(engine.USE_GRAPH[0]),
+                  "concurrent_downsample": bool(engine.CONCURRENT_DS[0]),
+                  "batch_slices_on_streams": engine.STREAMS[0],
+                  "distinct_batches": len(xs),
+                  "calibrations_total": stats["calibrations"],
+                  "timed_calibrations": timed_stats["calibrations"],
+                  "timed_overflow_reruns": timed_stats["overflow_reruns"],
+                  "timed_stale_reruns": timed_stats["stale_reruns"],
+                  "timed_graph_captures": timed_stats["graph_captures"],
+                  "tile_table": ops.tile_table_info()}
+        res = {
+            "metric": METRIC,
+            "value": round(value, 2),
+            "unit": "images/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 4),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "i8",
+            "data": "synthetic (N(0,1) 224x224 on device; seeded random-init weights, reference init)",
+            "full": bool(args.full),
+            "config": config,
+        }
+        if roof is not None:
+            config["quantized_convs_per_step"] = roof["launches_per_step"]
+            res["roofline"] = roof
+        return res
+
+    if not args.full:
+        lockstep.close()
+        if rank == 0:
+            print(json.dumps(result(None)), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # per-launch kernel durations for the roofline: the same forward, launched eagerly, one launch
     # at a time (events time each kernel alone). Region 1: the whole batch per launch (for
@@ -363,9 +435,6 @@ def main():
     timer = eager_region(nst)
     lockstep.close()
     iso = timer.roofline(args.roofline_steps)
-    images = args.batch * world * args.steps
-    value = images / elapsed
-    ms_per_step = elapsed / args.steps * 1e3
     # The roofline of the timed region: its per-launch time = the event-timed GPU time of a step
     # divided by the step's launches (the two batch slices run concurrently, so a launch's share of
     # the step, not its isolated duration, is what the throughput is made of); its algorithmic
@@ -408,36 +477,7 @@ def main():
     roof["int8_fused_floor_ms"] = round(fms * args.batch / fb, 4)
     roof["int8_fused_frac"] = round(roof["int8_fused_floor_ms"] / ms_per_step, 4)
     if rank == 0:
-        res = {
-            "metric": METRIC,
-            "value": round(value, 2),
-            "unit": "images/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "i8",
-            "data": "synthetic (N(0,1) 224x224 on device; seeded random-init weights, reference init)",
-            "config": {"workload": desc, "assignment": assign, "batch_per_gpu": args.batch,
-                       "global_batch": args.batch * world, "act_limbs": args.limbs,
-                       "act_code": {1: "int8", 2: "int16 (2 int8 limbs)", 3: "int24 (3 int8 limbs)"}[args.limbs],
-                       "parallelism": "dp%d" % world, "quantized_convs_per_step": roof["launches_per_step"],
-                       "range_mode": engine.get_range_mode(), "chunk": engine.CHUNK[0],
-                       "hip_graph": bool(engine.USE_GRAPH[0]),
-                       "concurrent_downsample": bool(engine.CONCURRENT_DS[0]),
-                       "batch_slices_on_streams": engine.STREAMS[0],
-                       "distinct_batches": len(xs),
-                       "calibrations_total": stats["calibrations"],
-                       "timed_calibrations": timed_stats["calibrations"],
-                       "timed_overflow_reruns": timed_stats["overflow_reruns"],
-                       "timed_stale_reruns": timed_stats["stale_reruns"],
-                       "timed_graph_captures": timed_stats["graph_captures"],
-                       "tile_table": ops.tile_table_info()},
-            "roofline": roof,
-        }
+        res = result(roof)
         if not args.no_cpu_baseline and world == 1:
             res["cpu_baseline"] = cpu_baseline(arch, assign, args.batch, args.cpu_iters)
         print(json.dumps(res), flush=True)

@@ -34,12 +34,12 @@ for step in "$@"; do
   case "$step" in
     gputests) run 900 $o.log $PYT tests -m gpu ;;
     smoke) run 300 $o.log python -u -c "import __graft_entry__ as g; g.build(); g.smoke()" ;;
-    bench) run 300 $o.json sh -c "python -u bench.py --layers 2> $o.err" ;;
-    r18) run 300 $o.json sh -c "python -u bench.py --config r18_u8 --no-cpu-baseline --layers 2> $o.err" ;;
-    r34) run 300 $o.json sh -c "python -u bench.py --config r34_4bit --batch 512 --no-cpu-baseline --layers 2> $o.err" ;;
+    bench) run 300 $o.json sh -c "python -u bench.py --full --layers 2> $o.err" ;;
+    r18) run 300 $o.json sh -c "python -u bench.py --full --config r18_u8 --no-cpu-baseline --layers 2> $o.err" ;;
+    r34) run 300 $o.json sh -c "python -u bench.py --full --config r34_4bit --batch 512 --no-cpu-baseline --layers 2> $o.err" ;;
     trace)
       run 300 $o.log rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/${tag}_prof -o run -- \
-        python3 bench.py --no-cpu-baseline
+        python3 bench.py --full --no-cpu-baseline
       f=$(find gpurun_out/${tag}_prof -name run_kernel_stats.csv | head -n 1)
       t=$(find gpurun_out/${tag}_prof -name run_kernel_trace.csv | head -n 1)
       python tools/rocprof_summary.py "$f" "$t" 106 > $o.summary.txt 2>&1

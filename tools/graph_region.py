@@ -3,7 +3,7 @@
 
 usage: python tools/graph_region.py <run_kernel_trace.csv> [launches_per_slice steps rsteps slices]
 
-bench.py's tail in the trace (round 5): [timed: steps graph replays, each `slices` batch slices
+bench.py --full's tail in the trace (round 5): [timed: steps graph replays, each `slices` batch slices
 of `launches_per_slice` quantized convs on their own queues] [whole-batch eager region: 1 + rsteps
 steps] [roofline region: 1 + rsteps steps of the same slices, one launch at a time]. A slice is a
 dependency chain (its kernels never overlap each other); the chains run concurrently, one per

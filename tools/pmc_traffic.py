@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""HBM traffic per quantized-conv launch from two rocprofv3 --pmc passes over bench.py
+"""HBM traffic per quantized-conv launch from two rocprofv3 --pmc passes over bench.py --full
 (FETCH_SIZE in one pass, WRITE_SIZE in another — they do not fit one pass on gfx950).
 
 Corrections (MI355X_MICROARCH.md 'HBM [CDNA4]'): FETCH_SIZE and WRITE_SIZE are in KiB;
@@ -7,7 +7,7 @@ FETCH_SIZE reports half the bytes of wide (16 B/lane) streaming reads on gfx950 
 `buffer_load_dwordx4 ... lds` operand DMA and the 16-B residual loads are of that kind), so it is
 doubled; WRITE_SIZE is exact for 16-B/lane stores (the limb-plane copy-out is).
 
-The launches compared are the last `rsteps x launches` quantized-conv dispatches — bench.py's
+The launches compared are the last `rsteps x launches` quantized-conv dispatches — bench.py --full's
 event-timed eager roofline region — so the traffic and `roofline.achieved` cover the same
 kernels. Writes profiles/<out>.json, which bench.py copies into roofline.traffic.
 

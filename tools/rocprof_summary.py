@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Summarize a rocprofv3 --kernel-trace --stats run of bench.py: per-kernel totals and the
+"""Summarize a rocprofv3 --kernel-trace --stats run of bench.py --full: per-kernel totals and the
 average duration of the quantized-conv launches (to check bench.py's event-timed avg_launch_ms).
 usage: python tools/rocprof_summary.py <run_kernel_stats.csv> [run_kernel_trace.csv [L steps rsteps]]"""
 import csv
