@@ -390,6 +390,63 @@ int smpq_fingerprint(const void* const* ptrs, const int64_t* nbytes, int ntensor
 int smpq_fingerprint_compare(const uint64_t* a, const uint64_t* b, int n, int32_t* flag, smpq_stream_t stream);
 uint64_t smpq_fingerprint_host(const void* p, int64_t nbytes);
 
+/* ---- bit-packed weight store, format "smpq-packed/1" (normative) ---------------------------------
+ * The fake-quantized fp32 weights the search produces (functions.py:9-43) are exact multiples of
+ * their channel's step, so a b-bit channel needs b bits per weight, not 32: the in-memory snapshot
+ * the search's save / rollback uses (resnet50_main.py:212, :233-234) and the on-disk export
+ * (smpq/checkpoint.py snapshot / restore_ / save_packed / load_packed). Bit-exact both ways.
+ *
+ * One fp32 weight viewed as [cout][k], k = cin*kh*kw in the tensor's own [cin][kh][kw] order, is
+ * stored as five per-channel arrays and a payload of 32-bit words:
+ *   qbits    int8  [cout]    verbatim copy of the conv's metadata
+ *   step     fp32  [cout]    verbatim copy of the conv's metadata
+ *   mode     int8  [cout]    0 = raw; 1..8 = packed with that many bits per code
+ *   base     int32 [cout]    smallest code m of the channel; 0 for raw channels
+ *   word_off int64 [cout+1]  offsets into the payload in 32-bit words: the exclusive prefix sum of
+ *                            the per-channel word counts (word_off[0] = 0, word_off[cout] = total)
+ * Channel c is PACKED with b = qbits[c] when all of these hold, and RAW otherwise:
+ *   1. 1 <= b <= 8;
+ *   2. step[c] is finite and > 0;
+ *   3. every value v of the channel is finite;
+ *   4. m = rintf(v / step) (IEEE fp32 division, round half to even) satisfies |m| <= 2^23;
+ *   5. the bit pattern of fl32((float)m * step), m taken as the integer code, equals the bit
+ *      pattern of v (bits, not floats: a -0.0 weight is off-grid, since the code 0 gives +0.0);
+ *   6. max m - min m <= 2^b - 1.
+ * Raw therefore covers never-quantized channels (the stem, the downsample convs), a channel whose
+ * codes span 2^b + 1 levels after the quantizer's rounding (functions.py:41 ties), and a channel
+ * that is off its grid by one ulp.
+ * Payload: every channel starts on a word boundary at word_off[c].
+ *   packed   ceil(k*b / 32) words; code u_i = m_i - base occupies bits [i*b, (i+1)*b) of the
+ *            channel's little-endian bit stream, stream bit j being bit j % 32 of word j / 32;
+ *            unused high bits of the last word are zero
+ *   raw      k words: the IEEE bit patterns of the values
+ * Unpacking: w_i = fl32((float)(base + u_i) * step), one rounded multiply with no contraction,
+ * which condition 5 makes bitwise the original; raw channels copy their words back.
+ *
+ * Entry points (caller-owned pointers, the caller's stream, no allocation; k <= 2^26; payload
+ * and every array naturally aligned):
+ *   smpq_bitpack_plan   applies the six conditions: mode, base and words[c] = the channel's payload
+ *                       word count (int32 [cout]); one workgroup per channel
+ *   smpq_bitpack_store  writes exactly the words word_off plans (each once, no atomics) and
+ *                       nothing else; mode / base as planned for this w and step
+ *   smpq_bitpack_load   payload -> w; an element reads the one or two words holding its code (the
+ *                       second only when the code straddles it), never past word_off[cout]
+ * The *_host twins are native C++ with the same arithmetic, for weights in host memory. The
+ * caller guarantees mode in 0..8 and a word_off consistent with mode and k
+ * (checkpoint.load_packed validates a file before any kernel runs). */
+int smpq_bitpack_plan(const float* w, int cout, int k, const int8_t* qbits, const float* step, int8_t* mode,
+                      int32_t* base, int32_t* words, smpq_stream_t stream);
+int smpq_bitpack_store(const float* w, int cout, int k, const int8_t* mode, const int32_t* base, const float* step,
+                       const int64_t* word_off, uint32_t* payload, smpq_stream_t stream);
+int smpq_bitpack_load(const uint32_t* payload, int cout, int k, const int8_t* mode, const int32_t* base,
+                      const float* step, const int64_t* word_off, float* w, smpq_stream_t stream);
+int smpq_bitpack_plan_host(const float* w, int cout, int k, const int8_t* qbits, const float* step, int8_t* mode,
+                           int32_t* base, int32_t* words);
+int smpq_bitpack_store_host(const float* w, int cout, int k, const int8_t* mode, const int32_t* base,
+                            const float* step, const int64_t* word_off, uint32_t* payload);
+int smpq_bitpack_load_host(const uint32_t* payload, int cout, int k, const int8_t* mode, const int32_t* base,
+                           const float* step, const int64_t* word_off, float* w);
+
 /* Diagnostics: one v_mfma_i32_16x16x64_i8 with the kernel's fragment mapping.
  *   a [16][64] int8 row-major, b [16][64] int8 (b[col][k]), c [16][16] int32 row-major */
 int smpq_debug_mfma_i8(const int8_t* a, const int8_t* b, int32_t* c, smpq_stream_t stream);

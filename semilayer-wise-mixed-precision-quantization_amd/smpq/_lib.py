@@ -84,6 +84,12 @@ _PROTOS = {
     "smpq_fingerprint": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp]),
     "smpq_fingerprint_compare": (_i, [_vp, _vp, _i, _vp, _vp]),
     "smpq_fingerprint_host": (ctypes.c_uint64, [_vp, _i64]),
+    "smpq_bitpack_plan": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "smpq_bitpack_store": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "smpq_bitpack_load": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "smpq_bitpack_plan_host": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "smpq_bitpack_store_host": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "smpq_bitpack_load_host": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
 }
 
 

@@ -918,3 +918,110 @@ def avgpool_fc(x_nhwc, weight, bias, out=None):
                                                _lib.ptr(pooled), _lib.ptr(out), _lib.stream_ptr()),
                    "smpq_avgpool_fc")
     return out
+
+
+# ---- bit-packed weight store, format smpq-packed/1 (include/smpq.h) ----------------------------
+# Every function takes the weight's device from its tensors: the HIP kernels for device tensors,
+# the native host twins for host tensors. Outputs are allocated here as int8 (byte) buffers.
+BITPACK_MAX_K = 1 << 26
+
+
+def _bp_meta(cout, dev, **named):
+    """The per-channel arrays of one weight: dtype, length, device, contiguity."""
+    want = {"qbits": torch.int8, "mode": torch.int8, "base": torch.int32, "step": torch.float32}
+    for name, t in named.items():
+        if name == "word_off":
+            _req(t.dtype == torch.int64 and t.numel() == cout + 1 and t.device == dev and t.is_contiguous(),
+                 "bitpack: word_off must be a contiguous int64 [cout + 1] tensor on the weight's device")
+        else:
+            _req(t.dtype == want[name] and t.numel() == cout and t.device == dev and t.is_contiguous(),
+                 "bitpack: %s must be a contiguous %s [cout] tensor on the weight's device" % (name, want[name]))
+
+
+def _bp_weight(w2d, what):
+    _req(w2d.dtype == torch.float32 and w2d.dim() == 2 and w2d.is_contiguous() and w2d.numel() > 0,
+         "%s: need a contiguous fp32 [cout, k] tensor" % what)
+    _req(w2d.shape[1] <= BITPACK_MAX_K, "%s: k above 2^26" % what)
+    return int(w2d.shape[0]), int(w2d.shape[1])
+
+
+def bitpack_plan(w2d, qbits, step):
+    """Which channels of ``w2d`` (fp32 [cout, k]) pack at their recorded bit-width (the six
+    conditions of include/smpq.h): (mode int8 [cout], base int32 [cout], words int32 [cout] = each
+    channel's payload word count), on w2d's device."""
+    cout, k = _bp_weight(w2d, "bitpack_plan")
+    dev = w2d.device
+    _bp_meta(cout, dev, qbits=qbits, step=step)
+    mode = torch.empty(cout, dtype=torch.int8, device=dev)
+    base = torch.empty(4 * cout, dtype=torch.int8, device=dev).view(torch.int32)
+    words = torch.empty(4 * cout, dtype=torch.int8, device=dev).view(torch.int32)
+    lib = _lib.load()
+    P = _lib.ptr
+    if w2d.is_cuda:
+        with torch.cuda.device(dev):
+            _lib.check(lib.smpq_bitpack_plan(P(w2d), cout, k, P(qbits), P(step), P(mode), P(base), P(words),
+                                             _lib.stream_ptr()), "smpq_bitpack_plan")
+    else:
+        _lib.check(lib.smpq_bitpack_plan_host(P(w2d), cout, k, P(qbits), P(step), P(mode), P(base), P(words)),
+                   "smpq_bitpack_plan_host")
+    return mode, base, words
+
+
+def bitpack_offsets(words):
+    """word_off int64 [cout + 1]: the exclusive prefix sum of the per-channel word counts (no host
+    sync); word_off[-1] is the payload's length in words."""
+    off = torch.zeros(words.numel() + 1, dtype=torch.int64, device=words.device)
+    torch.cumsum(words, 0, dtype=torch.int64, out=off[1:])
+    return off
+
+
+def bitpack_store(w2d, mode, base, step, word_off, total_words=None):
+    """The payload of ``w2d`` under a plan: int8 [4 * total_words] (the byte view of the 32-bit
+    words). ``total_words`` = word_off[-1] when the caller already has it on the host (one host
+    sync here otherwise)."""
+    cout, k = _bp_weight(w2d, "bitpack_store")
+    dev = w2d.device
+    _bp_meta(cout, dev, mode=mode, base=base, step=step, word_off=word_off)
+    total = int(word_off[-1].item()) if total_words is None else int(total_words)
+    _req(cout <= total <= cout * k, "bitpack_store: total_words outside [cout, cout * k]")
+    payload = torch.empty(4 * total, dtype=torch.int8, device=dev)
+    _req(payload.data_ptr() % 4 == 0, "bitpack_store: payload not word aligned")
+    lib = _lib.load()
+    P = _lib.ptr
+    if w2d.is_cuda:
+        with torch.cuda.device(dev):
+            _lib.check(lib.smpq_bitpack_store(P(w2d), cout, k, P(mode), P(base), P(step), P(word_off), P(payload),
+                                              _lib.stream_ptr()), "smpq_bitpack_store")
+    else:
+        _lib.check(lib.smpq_bitpack_store_host(P(w2d), cout, k, P(mode), P(base), P(step), P(word_off), P(payload)),
+                   "smpq_bitpack_store_host")
+    return payload
+
+
+def bitpack_load(payload, cout, k, mode, base, step, word_off, out=None):
+    """Unpack a payload (int8 bytes of the 32-bit words) into fp32 [cout, k]: a new tensor on the
+    payload's device, or ``out`` (a contiguous fp32 tensor of cout * k elements there, e.g. a conv
+    weight, written in place). The caller vouches for mode / word_off (checkpoint.load_packed
+    validates files); no host sync."""
+    cout, k = int(cout), int(k)
+    dev = payload.device
+    _req(payload.dtype == torch.int8 and payload.dim() == 1 and payload.is_contiguous()
+         and payload.numel() % 4 == 0 and payload.data_ptr() % 4 == 0,
+         "bitpack_load: payload must be a contiguous, word-aligned int8 tensor of whole words")
+    _req(cout > 0 and 0 < k <= BITPACK_MAX_K and 4 * cout <= payload.numel() <= 4 * cout * k,
+         "bitpack_load: payload length does not fit [cout, k]")
+    _bp_meta(cout, dev, mode=mode, base=base, step=step, word_off=word_off)
+    if out is None:
+        out = torch.empty(cout, k, dtype=torch.float32, device=dev)
+    _req(out.dtype == torch.float32 and out.numel() == cout * k and out.is_contiguous() and out.device == dev,
+         "bitpack_load: out must be a contiguous fp32 tensor of cout * k elements on the payload's device")
+    lib = _lib.load()
+    P = _lib.ptr
+    if payload.is_cuda:
+        with torch.cuda.device(dev):
+            _lib.check(lib.smpq_bitpack_load(P(payload), cout, k, P(mode), P(base), P(step), P(word_off), P(out),
+                                             _lib.stream_ptr()), "smpq_bitpack_load")
+    else:
+        _lib.check(lib.smpq_bitpack_load_host(P(payload), cout, k, P(mode), P(base), P(step), P(word_off), P(out)),
+                   "smpq_bitpack_load_host")
+    return out

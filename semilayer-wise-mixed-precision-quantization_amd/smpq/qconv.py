@@ -105,6 +105,22 @@ class QConv2d(nn.Conv2d):
         self._bits_host[:] = 0
         self._meta_gen += 1
 
+    def restore_quant(self, bits_host, qbits=None, qstep=None):
+        """Put back recorded metadata as a whole (checkpoint.restore_ / load_packed): ``bits_host``
+        the host mirror of qbits, ``qbits`` / ``qstep`` tensors [cout] on any device (None: the
+        caller has already copied them into the buffers, e.g. for every conv in one batched copy).
+        No host sync. The caller has rewritten the weight in place (a raw write, invisible to
+        ``_version``), so the content generation moves too: packed codes, ranges and graphs are
+        rebuilt."""
+        with torch.no_grad():
+            if qbits is not None:
+                self.qbits.copy_(qbits)
+            if qstep is not None:
+                self.qstep.copy_(qstep)
+        self._bits_host = np.asarray(bits_host).astype(np.int16).copy()
+        self._meta_gen += 1
+        self._content_gen += 1
+
     def fully_quantized(self):
         return bool((self._bits_host > 0).all())
 
