@@ -74,7 +74,12 @@ const char* smpq_build_stamp(void);
  *   w          device fp32 [cout][k_elems] (one output channel per row)
  *   bits       device int8 [cout]; 0 leaves the channel untouched
  *   scale_out  device fp32 [cout]; receives fp32(scale) of the quantization applied
- *   status     device int32 [1], caller-zeroed; set to (first constant channel)+1 */
+ *   status     device int32 [1], caller-zeroed; set to (lowest constant channel)+1, whatever order
+ *              the channels' workgroups run in (an atomic minimum over the non-zero reports)
+ * On that error every non-constant channel of the call is quantized all the same (its scale_out
+ * written) and the constant channels are left untouched with their scale_out unwritten: the channels
+ * run in parallel and none waits for another. (The host twin below stops at the first constant
+ * channel instead, as the reference's loop does.) */
 int smpq_quantize_channels_ex(float* w, int cout, int k_elems, const int8_t* bits,
                               float* scale_out, int32_t* status, int semantics, smpq_stream_t stream);
 
@@ -85,7 +90,8 @@ int smpq_quantize_channels(float* w, int cout, int k_elems, const int8_t* bits,
 /* Host-memory twin of smpq_quantize_channels (same arithmetic, native C++), used when the
  * weight lives in host memory (the reference quantizes CPU tensors of fresh models, e.g.
  * functions.py:504-512 right after resnet.resnet50(...) at :528). Returns SMPQ_E_CONSTANT on
- * a constant channel (channels before it are already quantized, as in the reference loop). */
+ * the lowest constant channel, which the error message names (channels before it are already
+ * quantized, that channel and every later one untouched, as in the reference loop). */
 int smpq_quantize_channels_host_ex(float* w, int cout, int k_elems, const int8_t* bits,
                                    float* scale_out, int semantics);
 
@@ -303,12 +309,17 @@ int smpq_stem_pool_s2d_q(const int8_t* xq, const float* x_absmax, int n, int h, 
                          int8_t* yq, float yq_range, int32_t* overflow, smpq_stream_t stream);
 
 /* AdaptiveAvgPool2d(1) + flatten + fc (ResNet._forward_impl resnet.py:216-218; modules built at
- * resnet.py:162-163) on the last block's NHWC fp32 output x [n][hw][c]: pooled[n][c] = (sum over
- * the hw pixels in order) * (1 / hw), logits[n][nout] = pooled . fc_w[nout][c] (+ fc_b[nout]),
- * summed over c in order with fused multiply-adds. Every logit is computed in an order that does
- * not depend on n or on the other images, so an image's logits are the same bits whatever batch
- * or data-parallel shard it runs in. pooled_ws: device fp32 [n][c] (workspace, holds the pooled
- * features afterwards); fc_b may be NULL; c % 4 == 0. */
+ * resnet.py:162-163) on the last block's NHWC fp32 output x [n][hw][c]: pooled[n][c] = (fp32 sum
+ * over the hw pixels) / hw, the division by hw correctly rounded (not a multiply by 1 / hw);
+ * logits[n][nout] = pooled . fc_w[nout][c] (+ fc_b[nout]) in fp32. Guaranteed: the order of every
+ * sum is fixed by hw and c alone (today: the pixels in order; the dot product as four partial sums
+ * over quarters of c, added in quarter order), never by n, nout or the other images, so an image's
+ * logits are the same bits whatever batch or data-parallel shard it runs in; and the bias is added
+ * last, in one rounded fp32 addition, so the logits with a bias are bitwise the logits without it
+ * + fc_b. The order itself is not part of the contract: each pooled feature is within
+ * (hw + 1) u (sum |x|) / hw and each logit within (hw + c + 2) u (sum_k P_k |w_k| + |b|) of the
+ * exact value, u = 2^-24, P_k = (sum over pixels |x_k|) / hw (tests/tail_ref.py). pooled_ws: device
+ * fp32 [n][c] (workspace, holds the pooled features afterwards); fc_b may be NULL; c % 4 == 0. */
 int smpq_avgpool_fc(const float* x, int n, int hw, int c, const float* fc_w, const float* fc_b, int nout,
                     float* pooled_ws, float* logits, smpq_stream_t stream);
 
@@ -361,11 +372,16 @@ size_t smpq_conv2d_workspace_bytes(int n, int h, int w, int cin, int cout, int k
  *   stats  double [4], ACCUMULATED (+=): [0] batch-mean cross entropy (criterion(output, y),
  *          :116 — one term per call, as loss_sum += loss at :121), [1] rows whose first maximal
  *          class equals the label (output.max(1), :114), [2] rows, [3] batches (+1)
- *   row_ws fp32 workspace [2 * rows]
+ *   row_ws fp32 workspace [2 * rows]; afterwards row_ws[row] is the row's loss
+ *          log(sum) + max - x[label] (NaN for a label outside [0, cols)) and row_ws[rows + row] is
+ *          1.0 when the row's first maximal class equals its label, else 0.0
  * smpq_kl_rows: stats double [2] += {sum over rows of sum_c p_ref * log(p_ref / p), rows}
- *   (functions.py:140-146; KLdiv = stats[0] / stats[1]); row_ws fp32 [rows].
+ *   (functions.py:140-146; KLdiv = stats[0] / stats[1]); row_ws fp32 [rows], afterwards the rows'
+ *   sums. The terms follow IEEE arithmetic as the reference's do: p = 0 where p_ref > 0 makes the
+ *   row +inf, and p_ref = 0 makes it NaN (0 * log 0), whatever p is there.
  * Rows are reduced in a fixed order in double: results do not depend on launch timing. A label
- * outside [0, cols) makes that row's loss NaN (the reference raises). */
+ * outside [0, cols) makes that row's loss NaN (the reference raises), and with it stats[0]; the
+ * other rows' row_ws entries and stats[1..3] are unaffected. */
 int smpq_softmax_xent(const float* logits, const int64_t* labels, int rows, int cols, float* probs,
                       double* stats, float* row_ws, smpq_stream_t stream);
 int smpq_kl_rows(const float* p_ref, const float* p, int rows, int cols, double* stats, float* row_ws,

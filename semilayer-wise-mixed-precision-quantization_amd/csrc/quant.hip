@@ -65,7 +65,17 @@ __global__ __launch_bounds__(kQThreads) void quantize_channels_kernel(
   }
   block_minmax(mn, mx, smem);
   if (mx == mn) {  // reference: ZeroDivisionError at functions.py:40
-    if (threadIdx.x == 0) atomicCAS(reinterpret_cast<int*>(status), 0, c + 1);
+    // status keeps the LOWEST constant channel + 1, whatever order the blocks arrive in: store
+    // c + 1 over 0 or over a higher channel's report, give way to a lower one
+    if (threadIdx.x == 0) {
+      int* st = reinterpret_cast<int*>(status);
+      int seen = 0;
+      for (;;) {
+        const int old = atomicCAS(st, seen, c + 1);
+        if (old == seen || (old != 0 && old <= c + 1)) break;
+        seen = old;
+      }
+    }
     return;
   }
   const double scale = ((double)mx - (double)mn) / (double)((1 << b) - 1);

@@ -185,20 +185,12 @@ def test_imagenet_synthetic_is_opt_in(monkeypatch):
 
 def test_host_fingerprint_formula(built_lib):
     # smpq_fingerprint_host = sum_i H(w_i, i) mod 2^64 (the device kernel's formula, include/smpq.h)
+    # (the plain-integer formula lives in tests/tail_ref.py, next to the vectorised reference)
     from smpq.fingerprint import host_fingerprint
-    M = (1 << 32) - 1
-
-    def fmix32(h):
-        h ^= h >> 16
-        h = (h * 0x85EBCA6B) & M
-        h ^= h >> 13
-        h = (h * 0xC2B2AE35) & M
-        return h ^ (h >> 16)
+    from tail_ref import fingerprint_scalar
 
     t = torch.randn(1000, generator=torch.Generator().manual_seed(3))
-    w = t.numpy().view(np.uint32).tolist()
-    exp = sum(fmix32(x ^ ((i * 0x9E3779B9) & M)) | (fmix32(x ^ ((i * 0x85EBCA6B + 0xC2B2AE35) & M)) << 32)
-              for i, x in enumerate(w)) % (1 << 64)
+    exp = fingerprint_scalar(t.numpy().view(np.uint32).tolist())
     assert host_fingerprint(t) == exp
     t2 = t.clone()
     t2[999] = torch.nextafter(t2[999], torch.tensor(1e9))
