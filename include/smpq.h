@@ -463,6 +463,39 @@ int smpq_bitpack_store_host(const float* w, int cout, int k, const int8_t* mode,
 int smpq_bitpack_load_host(const uint32_t* payload, int cout, int k, const int8_t* mode, const int32_t* base,
                            const float* step, const int64_t* word_off, float* w);
 
+/* ---- uint8 images through a per-channel table (normative) ----------------------------------------
+ * After Resize / CenterCrop / ToTensor / Normalize every pixel is one of 256 fp32 values per
+ * channel, so an evaluation set can be kept on the device as the uint8 it came from and replayed
+ * bit for bit (smpq/batches.py ResidentSet). Values are looked up, never recomputed.
+ *
+ * Data layout
+ *   A table is float lut[c][256] with 1 <= c <= 4. Every row is finite and strictly increasing
+ *   under `<`. Images are contiguous [n][c][hw]: x in fp32, u in uint8, same indexing;
+ *   ch(i) = (i / hw) % c is the channel of element i.
+ * smpq_u8lut_decode(u, n, c, hw, lut, x, stream)
+ *   x[i] = lut[ch(i)][u[i]]. Every element of x is written. Nothing else is written. u may start
+ *   at any byte and x at any multiple of 4 (views into larger buffers); 16-byte accesses are used
+ *   where both allow them and never straddle a channel plane. Stores are temporal.
+ * smpq_u8lut_encode(x, n, c, hw, lut, u, bad, stream)
+ *   For every element, u[i] is the largest v with lut[ch][v] <= x[i]. If there is no such v, or
+ *   x[i] is NaN, u[i] = 0. An element is ON THE GRID when the bit pattern of lut[ch][u[i]] equals
+ *   that of x[i] (bits, not floats: -0.0 against a +0.0 entry is off the grid). *bad (uint32,
+ *   zeroed by the caller) is increased by the number of off-grid elements: one atomic per
+ *   workgroup after a wave / workgroup reduction. Every byte of u is written, on the grid or not.
+ * smpq_u8lut_encode_host / smpq_u8lut_decode_host
+ *   Native twins with the same semantics for host memory. They validate the table and return
+ *   SMPQ_E_INVALID on a row that is not finite or not strictly increasing. The device entry
+ *   points cannot validate without a sync, so they trust the table (smpq.ops validates it).
+ * Sizes and return codes
+ *   n, c, hw >= 1, c <= 4 and n * c * hw < 2^31; anything else is SMPQ_E_SHAPE before a launch.
+ *   Null or misaligned pointers are SMPQ_E_INVALID. Caller-owned pointers, the caller's stream,
+ *   no allocation. */
+int smpq_u8lut_decode(const uint8_t* u, int n, int c, int hw, const float* lut, float* x, smpq_stream_t stream);
+int smpq_u8lut_encode(const float* x, int n, int c, int hw, const float* lut, uint8_t* u, uint32_t* bad,
+                      smpq_stream_t stream);
+int smpq_u8lut_decode_host(const uint8_t* u, int n, int c, int hw, const float* lut, float* x);
+int smpq_u8lut_encode_host(const float* x, int n, int c, int hw, const float* lut, uint8_t* u, uint32_t* bad);
+
 /* Diagnostics: one v_mfma_i32_16x16x64_i8 with the kernel's fragment mapping.
  *   a [16][64] int8 row-major, b [16][64] int8 (b[col][k]), c [16][16] int32 row-major */
 int smpq_debug_mfma_i8(const int8_t* a, const int8_t* b, int32_t* c, smpq_stream_t stream);

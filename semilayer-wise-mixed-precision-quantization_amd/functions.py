@@ -16,7 +16,7 @@ pass quantizing the caller's net for its first semilayer before switching to fre
 import torch
 
 from smpq import engine, ops
-from smpq.batches import DeviceBatches
+from smpq.batches import DeviceBatches, ResidentSet
 from smpq.models import ResNet
 from smpq.quant import channel_wise_quantizationperchan, quantize_wgt  # noqa: F401
 
@@ -27,8 +27,9 @@ def _run_eval(net, device, data_loader, want_probs):
     """Forward every batch, then the fused softmax / cross-entropy / top-1 kernel
     (smpq_softmax_xent) accumulates [loss_sum, correct, seen, batches] on the device: one host
     sync per evaluation. Host batches reach the device through DeviceBatches (the copy of the
-    next batch overlaps this batch's forward). Returns (stats float64 [4] on the device, list of
-    softmax outputs)."""
+    next batch overlaps this batch's forward); a smpq.batches.ResidentSet is iterated as it is (it
+    reads its loader once and serves later evaluations from the device). Returns (stats float64
+    [4] on the device, list of softmax outputs)."""
     net.to(device)
     net.eval()
     dev = torch.device(device)
@@ -38,7 +39,10 @@ def _run_eval(net, device, data_loader, want_probs):
     outputs = []
     if isinstance(net, ResNet):
         engine.new_evaluation(net)  # ranges from this pass's own first batch: history-independent
-    batches = DeviceBatches(data_loader, dev) if dev.type == "cuda" else data_loader
+    if isinstance(data_loader, ResidentSet):
+        batches = data_loader.bind(dev)  # (a CPU device is a ValueError: there is no CPU form)
+    else:
+        batches = DeviceBatches(data_loader, dev) if dev.type == "cuda" else data_loader
     with torch.no_grad():
         for x, y in batches:
             x = x.to(device, non_blocking=True)

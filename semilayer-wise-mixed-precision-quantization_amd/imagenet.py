@@ -8,6 +8,13 @@ synthetic stand-in of the same shape (N(0,1) 224x224 images, comparable to norma
 with seeded labels; ``SMPQ_SYNTH_IMAGES`` images, default 1024, in batches of ``SMPQ_BATCH``,
 default 256) is served only on explicit opt-in, ``SMPQ_SYNTHETIC=1`` (the build and GPU boxes
 have neither torchvision nor ImageNet), and announces itself on stderr.
+
+``SMPQ_RESIDENT_VAL=1`` (default off) wraps ``val_loader``, real or synthetic, in a
+``smpq.batches.ResidentSet``: the first evaluation reads the loader, every later one is served
+from the device with bitwise the same batches (uint8 where the images lie on the ToTensor /
+Normalize grid, as the real loader's do; fp32 otherwise), so an unmodified driver pays the loader
+once. It binds to the current device on first use; ``SMPQ_RESIDENT_MAX_GB`` caps the device memory
+it may take (beyond it the set falls back to reading the loader every time). Announced on stderr.
 """
 import os
 import sys
@@ -49,3 +56,10 @@ if os.environ.get("SMPQ_SYNTHETIC", "0") == "1":
     val_loader = SyntheticImageNet(int(os.environ.get("SMPQ_SYNTH_IMAGES", "1024")), BATCH)
 else:
     val_loader = _real_loader()  # raises like the reference when torchvision / the dataset is absent
+
+if os.environ.get("SMPQ_RESIDENT_VAL", "0") == "1":
+    from smpq.batches import ResidentSet
+    _max_gb = os.environ.get("SMPQ_RESIDENT_MAX_GB")
+    print("smpq imagenet: SMPQ_RESIDENT_VAL=1 -> val_loader is read once and then served from the device%s"
+          % ("" if _max_gb is None else " (at most %s GB)" % _max_gb), file=sys.stderr)
+    val_loader = ResidentSet(val_loader, max_bytes=None if _max_gb is None else int(float(_max_gb) * 1e9))

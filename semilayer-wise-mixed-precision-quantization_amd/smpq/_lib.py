@@ -90,6 +90,10 @@ _PROTOS = {
     "smpq_bitpack_plan_host": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "smpq_bitpack_store_host": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "smpq_bitpack_load_host": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "smpq_u8lut_decode": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    "smpq_u8lut_encode": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "smpq_u8lut_decode_host": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "smpq_u8lut_encode_host": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
 }
 
 

@@ -80,11 +80,20 @@ def sharded_eval(net, loader, rank, world, device=None, keep_probs=True):
     over the ranks (equal shards): each rank forwards its images, the fused softmax / CE / top-1
     kernel accumulates on its device, and one all-reduce of 4 doubles combines the ranks.
     Returns (acc, loss, this rank's softmax shards) — the shards stay where they were made and
-    feed sharded_kldiv, so no logits or probabilities cross xGMI."""
+    feed sharded_kldiv, so no logits or probabilities cross xGMI. ``loader`` may be a
+    smpq.batches.ResidentSet whose shard is this (rank, world); any other shard is a ValueError."""
     from smpq import engine, ops
-    from smpq.batches import DeviceBatches
+    from smpq.batches import DeviceBatches, ResidentSet
     from smpq.models import ResNet
     dev = device or torch.device("cuda", torch.cuda.current_device())
+    resident = isinstance(loader, ResidentSet)
+    if resident:
+        # the set already holds exactly this rank's rows of every batch (the loader is read once,
+        # not once per evaluation and rank): its batches are used as they come
+        if (loader.shard or (0, 1)) != (rank, world):
+            raise ValueError("smpq: sharded_eval as rank %d of %d on a ResidentSet with shard %r"
+                             % (rank, world, loader.shard))
+        loader.bind(dev)
     stats = torch.zeros(4, dtype=torch.float64, device=dev)
     probs = []
     if isinstance(net, ResNet):
@@ -98,7 +107,7 @@ def sharded_eval(net, loader, rank, world, device=None, keep_probs=True):
     with torch.no_grad(), lockstep():
         # this rank's shards reach the device as functions.evaluate_acc_loss_softmax's batches do:
         # the next one's copy on a side stream while this one runs
-        for x, y in DeviceBatches(shards(), dev):
+        for x, y in (loader if resident else DeviceBatches(shards(), dev)):
             out = net(x).float().contiguous()
             p = ops.softmax_xent(out, y, stats, want_probs=keep_probs)
             if keep_probs:

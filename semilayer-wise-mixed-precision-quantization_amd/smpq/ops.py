@@ -1025,3 +1025,93 @@ def bitpack_load(payload, cout, k, mode, base, step, word_off, out=None):
         _lib.check(lib.smpq_bitpack_load_host(P(payload), cout, k, P(mode), P(base), P(step), P(word_off), P(out)),
                    "smpq_bitpack_load_host")
     return out
+
+
+# ---- uint8 images through a per-channel table (include/smpq.h) ----------------------------------
+# After Resize / CenterCrop / ToTensor / Normalize a pixel is one of 256 fp32 values per channel:
+# an fp32 batch that lies on that grid is kept as uint8 and decoded back bit for bit.
+IMAGENET_MEAN = (0.485, 0.456, 0.406)
+IMAGENET_STD = (0.229, 0.224, 0.225)
+U8LUT_MAX_C = 4
+
+
+def u8lut_table(mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    """The fp32 [c, 256] table of ToTensor then Normalize on a uint8 pixel, computed by torch's own
+    fp32 CPU operators in their order: u / 255, minus mean_c, divided by std_c, each rounded to
+    fp32 (a fused restatement differs in most entries). Defaults: torchvision's ImageNet constants."""
+    m = torch.as_tensor(mean, dtype=torch.float32).reshape(-1, 1)
+    s = torch.as_tensor(std, dtype=torch.float32).reshape(-1, 1)
+    _req(m.numel() == s.numel() and 1 <= m.numel() <= U8LUT_MAX_C, "u8lut_table: need 1 to 4 means and as many stds")
+    t = torch.arange(256, dtype=torch.uint8).to(torch.float32).div(255)
+    lut = t.repeat(m.numel(), 1).sub_(m).div_(s)
+    _u8lut_check_table(lut)
+    return lut
+
+
+def _u8lut_check_table(lut):
+    """Validate a table on the host (one copy of 1 - 4 KB for a device table), once per tensor and
+    version: fp32 [c, 256], contiguous, every row finite and strictly increasing."""
+    _req(torch.is_tensor(lut) and lut.dtype == torch.float32 and lut.dim() == 2 and lut.shape[1] == 256
+         and 1 <= lut.shape[0] <= U8LUT_MAX_C and lut.is_contiguous(),
+         "u8lut: the table must be a contiguous fp32 [c, 256] tensor with 1 <= c <= 4")
+    if getattr(lut, "_smpq_u8lut_ok", None) == lut._version:  # set below, on the tensor itself
+        return
+    h = lut.detach().cpu()
+    _req(bool(torch.isfinite(h).all()) and bool((h[:, 1:] > h[:, :-1]).all()),
+         "u8lut: every table row must be finite and strictly increasing")
+    lut._smpq_u8lut_ok = lut._version
+
+
+def _u8lut_images(t, dtype, lut, what):
+    """(n, c, hw) of a contiguous [n, c, ...] image tensor of ``dtype`` on the table's device."""
+    _req(torch.is_tensor(t) and t.dtype == dtype and t.dim() >= 2 and t.is_contiguous() and t.numel() > 0,
+         "%s: need a non-empty contiguous %s [n, c, ...] tensor" % (what, dtype))
+    _req(t.device == lut.device, "%s: images and table on different devices" % what)
+    _req(t.shape[1] == lut.shape[0], "%s: %d channels against a table of %d rows" % (what, t.shape[1], lut.shape[0]))
+    _req(t.numel() < 2 ** 31, "%s: 2^31 elements or more" % what)
+    n, c = int(t.shape[0]), int(t.shape[1])
+    return n, c, t.numel() // (n * c)
+
+
+def u8lut_encode(x, lut, out=None):
+    """fp32 images [n, c, ...] -> (u, bad): u uint8 of x's shape with u = the largest v with
+    lut[c][v] <= x (0 when there is none or x is NaN), and bad = a uint32 count (an int32 [1]
+    tensor on x's device, so reading it is the caller's sync) of the elements whose bit pattern is
+    not lut[c][u]'s. ``out``: a contiguous uint8 tensor of x's shape to write u into."""
+    _u8lut_check_table(lut)
+    n, c, hw = _u8lut_images(x, torch.float32, lut, "u8lut_encode")
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    _req(torch.is_tensor(out) and out.dtype == torch.uint8 and out.shape == x.shape and out.is_contiguous()
+         and out.device == x.device, "u8lut_encode: out must be a contiguous uint8 tensor of x's shape on its device")
+    bad = torch.zeros(1, dtype=torch.int32, device=x.device)
+    lib = _lib.load()
+    P = _lib.ptr
+    if x.is_cuda:
+        with torch.cuda.device(x.device):
+            _lib.check(lib.smpq_u8lut_encode(P(x), n, c, hw, P(lut), P(out), P(bad), _lib.stream_ptr()),
+                       "smpq_u8lut_encode")
+    else:
+        _lib.check(lib.smpq_u8lut_encode_host(P(x), n, c, hw, P(lut), P(out), P(bad)), "smpq_u8lut_encode_host")
+    return out, bad
+
+
+def u8lut_decode(u, lut, out=None):
+    """uint8 images [n, c, ...] -> fp32 x of the same shape, x = lut[c][u]. ``out``: a contiguous
+    fp32 tensor of u's shape to write into (e.g. a view of a staging buffer); nothing outside it
+    is written. No host sync for a table already validated."""
+    _u8lut_check_table(lut)
+    n, c, hw = _u8lut_images(u, torch.uint8, lut, "u8lut_decode")
+    if out is None:
+        out = torch.empty(u.shape, dtype=torch.float32, device=u.device)
+    _req(torch.is_tensor(out) and out.dtype == torch.float32 and out.shape == u.shape and out.is_contiguous()
+         and out.device == u.device and out.data_ptr() % 4 == 0,
+         "u8lut_decode: out must be a contiguous fp32 tensor of u's shape on its device")
+    lib = _lib.load()
+    P = _lib.ptr
+    if u.is_cuda:
+        with torch.cuda.device(u.device):
+            _lib.check(lib.smpq_u8lut_decode(P(u), n, c, hw, P(lut), P(out), _lib.stream_ptr()), "smpq_u8lut_decode")
+    else:
+        _lib.check(lib.smpq_u8lut_decode_host(P(u), n, c, hw, P(lut), P(out)), "smpq_u8lut_decode_host")
+    return out
