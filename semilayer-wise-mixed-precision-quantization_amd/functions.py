@@ -15,7 +15,7 @@ pass quantizing the caller's net for its first semilayer before switching to fre
 """
 import torch
 
-from smpq import engine, ops
+from smpq import engine, memo, ops
 from smpq.batches import DeviceBatches, ResidentSet
 from smpq.models import ResNet
 from smpq.quant import channel_wise_quantizationperchan, quantize_wgt  # noqa: F401
@@ -29,12 +29,19 @@ def _run_eval(net, device, data_loader, want_probs):
     sync per evaluation. Host batches reach the device through DeviceBatches (the copy of the
     next batch overlaps this batch's forward); a smpq.batches.ResidentSet is iterated as it is (it
     reads its loader once and serves later evaluations from the device). Returns (stats float64
-    [4] on the device, list of softmax outputs)."""
+    [4] on the device, list of softmax outputs). With smpq.memo on, an evaluation of a ResidentSet
+    that repeats a recorded one returns that record (stats on the host, clones of its softmax
+    outputs) without iterating the set; every other case runs the loop below unchanged."""
     net.to(device)
     net.eval()
     dev = torch.device(device)
     if dev.type == "cuda" and dev.index is None:
         dev = torch.device("cuda", torch.cuda.current_device())
+    token = None
+    if memo.ENABLED[0]:  # SMPQ_EVAL_MEMO (off by default): a repeated evaluation launches nothing
+        token = memo.begin(net, dev, data_loader, want_probs)
+        if token is not None and token.entry is not None:
+            return memo.hit_result(token)
     stats = torch.zeros(4, dtype=torch.float64, device=dev)
     outputs = []
     if isinstance(net, ResNet):
@@ -50,6 +57,8 @@ def _run_eval(net, device, data_loader, want_probs):
             p = ops.softmax_xent(out, y, stats, want_probs=want_probs)
             if want_probs:
                 outputs.append(p)
+    if token is not None:  # a miss that ran to its end: recorded if the set now vouches for a replay
+        stats = memo.finish(token, stats, outputs)
     return stats, outputs
 
 

@@ -138,6 +138,7 @@ class ResidentSet:
         self._staging = None   # two flat fp32 buffers sized for the largest uint8-backed batch
         self._cache = None     # list of ("u8", u, y, shape) / ("raw", x, y, None) once a pass completed
         self._fallback = False
+        self._epoch = 0        # moves whenever the content later passes serve may have changed
         self._counts = dict.fromkeys(("images", "u8_batches", "raw_batches", "resident_bytes", "fp32_bytes",
                                       "off_grid_elements"), 0)
         self._passes = {"loader_passes": 0, "resident_passes": 0}
@@ -183,16 +184,20 @@ class ResidentSet:
             self._stream.synchronize()  # a decode in flight still reads the cache and writes the staging
         self._cache = self._staging = None
         self._fallback = False
+        self._epoch += 1
         for k in self._counts:
             self._counts[k] = 0
 
     def report(self):
         """images, batches kept as uint8 / raw, resident bytes of the kept images and the fp32
-        bytes they stand for, off-grid elements seen, loader passes and resident passes served."""
+        bytes they stand for, off-grid elements seen, loader passes and resident passes served, and
+        the epoch: a counter that moves whenever a cache is installed and in invalidate(), so
+        (id(set), epoch) names one fixed content (smpq.memo keys on it)."""
         r = dict(self._counts)
         r.update(self._passes)
         r["resident"] = self._cache is not None
         r["fallback"] = self._fallback
+        r["epoch"] = self._epoch
         return r
 
     def __iter__(self):
@@ -254,6 +259,7 @@ class ResidentSet:
                 self._staging = [torch.empty(need, dtype=torch.float32, device=self.dev) for _ in range(2)] \
                     if need else None
                 self._cache = entries
+                self._epoch += 1
         finally:
             if self._cache is None:  # abandoned, failed or over max_bytes: nothing is kept
                 for k in self._counts:

@@ -10,6 +10,8 @@ checked against the golden checksums in tests/test_models.py).
 ``ResNet.forward`` runs ``smpq.engine.forward_fused`` (one fused HIP launch per quantized conv)
 on GPU inputs in eval mode, and the plain module path otherwise.
 """
+import os as _os
+
 import torch
 import torch.nn as nn
 
@@ -182,19 +184,79 @@ class ResNet(nn.Module):
         return out
 
 
+# Pristine-model pool (SMPQ_PRISTINE_POOL=1 or set_pristine_pool(True); off by default). The search
+# builds a fresh pretrained model after every semilayer of every sensitivity pass (functions.py:528,
+# 581) and on every rejection before the first acceptance (resnet50_main.py:231): each time a full
+# kaiming initialisation and a torch.load, all overwritten a moment later. With the pool on, the
+# first pretrained model per (arch, keyword arguments, weight file identity) is built as always and
+# its loaded state kept as a private host copy; later ones build the module tree on the meta device
+# (no parameter initialisation runs), materialise it on the CPU and load that copy. Only the local
+# SMPQ_PRETRAINED_DIR source is pooled. The pooled path draws nothing from torch's global CPU
+# generator (the normal path does, through the initialisation it discards): the reason for opt-in.
+_POOL_ON = [_os.environ.get("SMPQ_PRISTINE_POOL", "0") == "1"]
+_POOL = {}  # (arch, kwargs, (resolved path, size, mtime_ns)) -> host state dict, never handed out
+_POOL_COUNTS = {"hits": 0, "misses": 0}
+
+
+def set_pristine_pool(on):
+    _POOL_ON[0] = bool(on)
+
+
+def clear_pristine_pool():
+    _POOL.clear()
+    for k in _POOL_COUNTS:
+        _POOL_COUNTS[k] = 0
+
+
+def pristine_pool_report():
+    """enabled, hits (models built from a master), misses (masters made), entries, host bytes held."""
+    r = dict(_POOL_COUNTS)
+    r.update(enabled=_POOL_ON[0], entries=len(_POOL),
+             bytes=sum(t.numel() * t.element_size() for sd in _POOL.values() for t in sd.values()))
+    return r
+
+
+def _file_identity(path):
+    path = _os.path.realpath(path)
+    st = _os.stat(path)
+    return (path, st.st_size, st.st_mtime_ns)
+
+
+def _from_master(block, layers, kwargs, master):
+    with torch.device("meta"):
+        model = ResNet(block, layers, **kwargs)  # the tree only: initialising a meta tensor is a no-op
+    model.to_empty(device="cpu")
+    model.load_state_dict(master)  # strict: every parameter and buffer is written (copied, not shared)
+    return model
+
+
 def _resnet(arch, block, layers, pretrained, progress, **kwargs):
+    local = _os.environ.get("SMPQ_PRETRAINED_DIR")
+    pool_key = None
+    if pretrained and local and _POOL_ON[0]:
+        path = _os.path.join(local, _os.path.basename(MODEL_URLS[arch]))
+        ident = _file_identity(path)
+        pool_key = (arch, repr(sorted(kwargs.items())), ident)
+        master = _POOL.get(pool_key)
+        if master is not None:
+            _POOL_COUNTS["hits"] += 1
+            return _from_master(block, layers, kwargs, master)
+        # a rewritten file makes a new key: its predecessors are of no more use
+        for k in [k for k in _POOL if k[:2] == pool_key[:2] and k[2][0] == ident[0]]:
+            del _POOL[k]
     model = ResNet(block, layers, **kwargs)
     if pretrained:
         # resnet.py:228-231: a download; offline boxes can point SMPQ_PRETRAINED_DIR at local files
-        import os
-        local = os.environ.get("SMPQ_PRETRAINED_DIR")
         if local:
-            path = os.path.join(local, os.path.basename(MODEL_URLS[arch]))
+            path = _os.path.join(local, _os.path.basename(MODEL_URLS[arch]))
             state_dict = torch.load(path, map_location="cpu", weights_only=True)
         else:
             from torch.hub import load_state_dict_from_url
             state_dict = load_state_dict_from_url(MODEL_URLS[arch], progress=progress)
         model.load_state_dict(state_dict, strict=False)
+        if pool_key is not None:
+            _POOL_COUNTS["misses"] += 1
+            _POOL[pool_key] = {k: v.detach().clone() for k, v in model.state_dict().items()}
     return model
 
 
