@@ -133,10 +133,13 @@ def settings():
             ("use_graph", engine.USE_GRAPH[0]), ("serial_slices", engine.SERIAL_SLICES[0]))
 
 
-def structure(net):
-    """Structural signature of the module tree: each module's name and type, each conv's geometry."""
+def structure(net, keep=None):
+    """Structural signature of the module tree: each module's name and type, each conv's geometry.
+    ``keep(name)``: only the modules it accepts (smpq.prefix: the modules upstream of a boundary)."""
     out = []
     for name, m in net.named_modules():
+        if keep is not None and not keep(name):
+            continue
         row = [name, type(m).__module__ + "." + type(m).__qualname__]
         if isinstance(m, torch.nn.Conv2d):
             row += [m.in_channels, m.out_channels, tuple(m.kernel_size), tuple(m.stride), tuple(m.padding),
@@ -189,17 +192,22 @@ def device_digests(net, named):
     return [next(it) if t.numel() > 0 else 0 for _, t in named]
 
 
-def state_key(net, digest=None):
-    """The content key of ``net`` under the current settings. ``digest(net, named)`` returns one
-    integer per (name, tensor) of ``state_dict()`` (default: the device fingerprints)."""
-    named = [(k, v.detach()) for k, v in net.state_dict().items()]
-    digests = (digest or device_digests)(net, named)
+def bits_rows(net):
+    """(name, dtype + shape + bytes) of every conv's host mirror of its bit-widths."""
     bits = []
     for name, m in net.named_modules():
         if isinstance(m, QConv2d):
             b = m._bits_host
             bits.append((name, ("%s%s" % (b.dtype.str, b.shape)).encode() + b.tobytes()))
-    return compose_key([(k, str(t.dtype), tuple(t.shape)) for k, t in named], digests, bits, structure(net),
+    return bits
+
+
+def state_key(net, digest=None):
+    """The content key of ``net`` under the current settings. ``digest(net, named)`` returns one
+    integer per (name, tensor) of ``state_dict()`` (default: the device fingerprints)."""
+    named = [(k, v.detach()) for k, v in net.state_dict().items()]
+    digests = (digest or device_digests)(net, named)
+    return compose_key([(k, str(t.dtype), tuple(t.shape)) for k, t in named], digests, bits_rows(net), structure(net),
                        settings())
 
 
