@@ -58,7 +58,7 @@ class DeviceBatches:
 
     def __iter__(self):
         it = iter(self.loader)
-        nxt = [None]
+        staged = [None]
 
         from .engine import CAPTURE_LOCK
 
@@ -67,16 +67,16 @@ class DeviceBatches:
                 x, y = next(it)  # the loader's own work (host only) runs beside anything
                 # device work waits for a graph capture on the main thread to end (engine.CAPTURE_LOCK)
                 with CAPTURE_LOCK, torch.cuda.device(self.dev):
-                    nxt[0] = self._stage(x, y)
+                    staged[0] = self._stage(x, y)
             except StopIteration:
-                nxt[0] = StopIteration
+                staged[0] = StopIteration
             except BaseException as e:  # noqa: BLE001 -- re-raised in the consuming thread
-                nxt[0] = e
+                staged[0] = e
         fetch()
-        while nxt[0] is not StopIteration:
-            if isinstance(nxt[0], BaseException):
-                raise nxt[0]
-            xd, yd, ev = nxt[0]
+        while staged[0] is not StopIteration:
+            if isinstance(staged[0], BaseException):
+                raise staged[0]
+            xd, yd, ev = staged[0]
             worker = threading.Thread(target=fetch)  # stage batch i+1 while batch i runs
             worker.start()
             main = torch.cuda.current_stream(self.dev)
@@ -286,14 +286,14 @@ class ResidentSet:
                 ev.record(side)
             ready[i] = (x, ev)
         decode(0)
-        for i, entry in enumerate(cache):
+        for i, (kind, data, y, _) in enumerate(cache):
             decode(i + 1)
-            if entry[0] == "u8":
+            if kind == "u8":
                 x, ev = ready.pop(i)
                 main.wait_event(ev)
             else:
-                x = entry[1]
+                x = data
             if i == len(cache) - 1:
                 self._passes["resident_passes"] += 1  # (the last batch handed out: the pass is served)
-            yield x, entry[2]
+            yield x, y
             main = torch.cuda.current_stream(self.dev)

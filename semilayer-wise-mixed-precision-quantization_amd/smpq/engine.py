@@ -34,7 +34,7 @@ Range modes (``set_range_mode``):
     and the forward is recomputed in dynamic mode, widening the ranges, so results are never
     silently clamped. Calibration is redone whenever a weight, BN buffer or the limb count changes.
 
-Cache validity: every cache (packed codes, folded BN, ranges, the captured graph) is keyed on the
+Cache validity: every cache (packed codes, folded BN; per model, in ModelState: ranges, captured graphs) is keyed on the
 identity, data_ptr and ``_version`` of every parameter and buffer of the model (a replaced
 Parameter, ``load_state_dict(assign=True)`` or a swapped submodule is seen), and on device-side
 content fingerprints of the conv weights / metadata / BN tensors (smpq/fingerprint.py), checked
@@ -42,6 +42,7 @@ after every forward: a write through ``.data`` (no version bump) is detected, th
 discarded and recomputed from freshly packed weights.
 """
 import threading
+from collections import namedtuple
 
 import torch
 import torch.nn.functional as F
@@ -80,15 +81,12 @@ PAIR_STAGE_ENTRY = [_os.environ.get("SMPQ_PAIR_STAGE_ENTRY", "1") != "0"]
 FUSE_DS = [_os.environ.get("SMPQ_FUSE_DS", "1") != "0"]
 # ... for the blocks whose conv3 has at most this many input channels (64: layer1, 128: + layer2)
 FUSE_DS_MAX_CIN = [int(_os.environ.get("SMPQ_FUSE_DS_MAX_CIN", "256"))]
-stats.setdefault("graph_captures", 0)
-stats.setdefault("graph_replays", 0)
+stats.update({k: stats.get(k, 0) for k in ("graph_captures", "graph_replays", "calibrations", "overflow_reruns",
+                                           "stale_reruns")})
 
 
 def set_chunk(n):
     CHUNK[0] = max(1, int(n))
-stats.setdefault("calibrations", 0)
-stats.setdefault("overflow_reruns", 0)
-stats.setdefault("stale_reruns", 0)
 
 
 def set_range_mode(mode):
@@ -129,29 +127,45 @@ def _bn_key(bn):
     return tuple((id(t), t.data_ptr(), t._version) for t in ts) + (bn.eps,)
 
 
+# What the fused kernel needs of a conv + its BN: weight codes, their offsets (or None), the folded
+# per-channel scale and shift, the codes' kind (QConv2d.packed); the space-to-depth stem has no offsets
+ConvPlan = namedtuple("ConvPlan", "codes offset col_scale col_shift kind")
+StemPlan = namedtuple("StemPlan", "codes col_scale col_shift kind")
+
+
+def _fold(conv, bn, wscale):
+    """(col_scale, col_shift): BN (or identity) folded onto the weight scales and the conv's bias."""
+    if bn is not None:
+        a, b = _bn_fold(bn)
+    else:
+        a, b = torch.ones_like(wscale), torch.zeros_like(wscale)
+    if conv.bias is not None:
+        b = b + conv.bias.float() * a
+    return (wscale * a).contiguous(), b.contiguous()
+
+
+def _cached_plan(conv, bn, attr, build):
+    """The plan kept on ``conv`` under ``attr`` while its packed codes, ``bn`` and its bias are what
+    the plan was folded from; otherwise ``build()`` (under no_grad), kept from now on."""
+    key = (conv._pack_key(), _bn_key(bn), None if conv.bias is None else (conv.bias.data_ptr(), conv.bias._version))
+    cache = getattr(conv, attr, None)
+    if cache is not None and cache[0] == key:
+        return cache[1]
+    with torch.no_grad():
+        plan = build()
+    setattr(conv, attr, (key, plan))
+    return plan
+
+
 def conv_plan(conv, bn):
-    """(codes, offset, col_scale, col_shift, kind) for the fused kernel, or None."""
+    """The ConvPlan of ``conv`` + ``bn`` for the fused kernel, or None."""
     if not isinstance(conv, QConv2d):
         return None
     pk = conv.packed()
     if pk is None:
         return None
-    key = (conv._pack_key(), _bn_key(bn), None if conv.bias is None else (conv.bias.data_ptr(), conv.bias._version))
-    cache = getattr(conv, "_fold_cache", None)
-    if cache is not None and cache[0] == key:
-        return cache[1]
     codes, _, offset, wscale, kind = pk
-    with torch.no_grad():
-        if bn is not None:
-            a, b = _bn_fold(bn)
-        else:
-            a = torch.ones_like(wscale)
-            b = torch.zeros_like(wscale)
-        if conv.bias is not None:
-            b = b + conv.bias.float() * a
-        plan = (codes, offset, (wscale * a).contiguous(), b.contiguous(), kind)
-    conv._fold_cache = (key, plan)
-    return plan
+    return _cached_plan(conv, bn, "_fold_cache", lambda: ConvPlan(codes, offset, *_fold(conv, bn, wscale), kind))
 
 
 def _to_nchw(x_nhwc):
@@ -186,6 +200,14 @@ class Ctx:
         return t
 
 
+def _record_max(ctx, conv, yam):
+    """A calibration forward (``ctx.record``): keep the largest of ``conv``'s per-image maxima."""
+    if ctx is not None and ctx.record is not None and yam is not None:
+        prev = ctx.record.get(id(conv))
+        m = yam.amax().reshape(1)
+        ctx.record[id(conv)] = m if prev is None else torch.maximum(prev, m)
+
+
 def run_conv(conv, bn, act, relu, residual=None, want_amax=True, ctx=None, want_f32=True):
     """y = act(bn(conv(x)) [+ residual]) -> Act (NHWC fp32 and/or the next conv's limb planes).
     ``residual``: an fp32 NHWC tensor, or an Act carrying limb planes + static range."""
@@ -206,21 +228,16 @@ def run_conv(conv, bn, act, relu, residual=None, want_amax=True, ctx=None, want_
         if kind == "fixed":
             stats["fixed_conv"] += 1
         conv.last_path = "hip-" + kind
+        args = (act.limbs(), act.amax, codes, offset, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0],
+                conv.padding[0], col_scale, col_shift)
         if static:
             rng = ctx.ranges[id(conv)]
-            y, yq = ops.tuned_conv2d_q(act.limbs(), act.amax, codes, offset, conv.kernel_size[0],
-                                       conv.kernel_size[1], conv.stride[0], conv.padding[0], col_scale, col_shift,
-                                       residual=residual, relu=relu, emit_range=rng, overflow=ctx.overflow,
+            y, yq = ops.tuned_conv2d_q(*args, residual=residual, relu=relu, emit_range=rng, overflow=ctx.overflow,
                                        want_f32=want_f32, residual_q=res_q, residual_range=res_rng)
             return Act(f32=y, q=yq, amax=ctx.range_tensor(conv), rng=rng)
-        y = ops.tuned_conv2d_q(act.limbs(), act.amax, codes, offset, conv.kernel_size[0], conv.kernel_size[1],
-                               conv.stride[0], conv.padding[0], col_scale, col_shift,
-                               residual=residual, relu=relu, y_absmax=yam, residual_q=res_q,
+        y = ops.tuned_conv2d_q(*args, residual=residual, relu=relu, y_absmax=yam, residual_q=res_q,
                                residual_range=res_rng)
-        if ctx is not None and ctx.record is not None and yam is not None:
-            prev = ctx.record.get(id(conv))
-            m = yam.amax().reshape(1)
-            ctx.record[id(conv)] = m if prev is None else torch.maximum(prev, m)
+        _record_max(ctx, conv, yam)
         return Act(f32=y, amax=yam)
     yam = torch.zeros(n, dtype=torch.float32, device=conv.weight.device) if want_amax else None
     # geometry the kernel does not cover: the reference's fp32 arithmetic on MIOpen
@@ -259,17 +276,12 @@ def _stream(key):
     return s
 
 
-def _side_stream(device, lane):
-    """The downsample branch's stream of batch slice ``lane`` (None: the unsliced forward)."""
-    return _stream((device, "ds", lane))
-
-
 def _1x1(c):
     return c.kernel_size == (1, 1) and c.stride == (1, 1) and c.padding == (0, 0) and c.groups == 1
 
 
 def _exact(plan):
-    return plan is not None and (plan[0].dim() == 2 or plan[0].shape[0] == 1)
+    return plan is not None and (plan.codes.dim() == 2 or plan.codes.shape[0] == 1)
 
 
 def _pair_plan(blk, nxt, ctx):
@@ -284,7 +296,7 @@ def _pair_plan(blk, nxt, ctx):
     if id(c3) not in ctx.ranges or id(c1) not in ctx.ranges or not (_1x1(c3) and _1x1(c1)):
         return None
     p3, p1 = conv_plan(c3, blk.bn3), conv_plan(c1, nxt.bn1)
-    if not (_exact(p3) and _exact(p1)) or p1[1] is not None:
+    if not (_exact(p3) and _exact(p1)) or p1.offset is not None:
         return None
     if not ops.conv_chain_supported(c3.in_channels, c3.out_channels, c1.out_channels):
         return None
@@ -309,7 +321,7 @@ def _ds_fuse_plan(blk, x, ctx):
             and id(dc) in ctx.ranges and id(c3) in ctx.ranges):
         return None
     pd, p3 = conv_plan(dc, dbn), conv_plan(c3, blk.bn3)
-    if pd is None or not _exact(p3) or pd[1] is not None or pd[0].dim() != 3 or pd[0].shape[0] != 3:
+    if pd is None or not _exact(p3) or pd.offset is not None or pd.codes.dim() != 3 or pd.codes.shape[0] != 3:
         return None
     if not ops.conv_chain_ds_supported(c3.in_channels, c3.out_channels, dc.in_channels, st):
         return None
@@ -349,7 +361,7 @@ def block_forward(blk, x, ctx=None, last=False, t1=None, nxt=None):
     elif blk.downsample is not None and CONCURRENT_DS[0] and ctx is not None and ctx.ranges is not None \
             and ctx.lane is None and x.q is not None:  # both branches read the input's limb planes
         main = torch.cuda.current_stream()
-        side = _side_stream(x.q.device, ctx.lane)
+        side = _stream((x.q.device, "ds", ctx.lane))  # the downsample branch's stream (lane None: unsliced)
         side.wait_stream(main)
         with torch.cuda.stream(side):
             # allocated on the side stream, consumed on main after the join; freed blocks are
@@ -386,29 +398,29 @@ def block_forward(blk, x, ctx=None, last=False, t1=None, nxt=None):
         if chain:
             # conv3 (+ identity, ReLU) with its downsample and / or the next block's conv1, one launch
             c3 = blk.conv3
-            codes3, off3, cs3, sh3, kind3 = conv_plan(c3, blk.bn3)
+            p3 = conv_plan(c3, blk.bn3)
             rng3, am3 = ctx.ranges[id(c3)], ctx.range_tensor(c3)
             dsarg = nxtarg = None
             if dsplan is not None:
-                dcodes, _, dcs, dsh, dkind = dsplan
-                dsarg = (x.q, x.amax, dcodes, dcs, dsh, ctx.ranges[id(blk.downsample[0])], st)
+                dsarg = ops.ChainDs(x.q, x.amax, dsplan.codes, dsplan.col_scale, dsplan.col_shift,
+                                    ctx.ranges[id(blk.downsample[0])], st)
             if p1 is not None:
-                nxtarg = (p1[0], p1[2], p1[3], ctx.ranges[id(nxt.conv1)])
-            yq3, yq1 = ops.conv_chain_q(t2.q, t2.amax, codes3, off3, cs3, sh3, rng3, am3, ctx.overflow,
-                                        residual_q=None if dsarg else identity.q,
+                nxtarg = ops.ChainNext(p1.codes, p1.col_scale, p1.col_shift, ctx.ranges[id(nxt.conv1)])
+            yq3, yq1 = ops.conv_chain_q(t2.q, t2.amax, p3.codes, p3.offset, p3.col_scale, p3.col_shift, rng3, am3,
+                                        ctx.overflow, residual_q=None if dsarg else identity.q,
                                         residual_range=None if dsarg else identity.rng, ds=dsarg, nxt=nxtarg)
             stats["hip_conv"] += 1 + (dsarg is not None) + (nxtarg is not None)
             stats["fixed_conv"] += dsarg is not None
             stats["chain_conv"] = stats.get("chain_conv", 0) + 1
             stats["pair_conv"] = stats.get("pair_conv", 0) + (nxtarg is not None)
             stats["fused_ds"] = stats.get("fused_ds", 0) + (dsarg is not None)
-            c3.last_path = "hip-%s-chain" % kind3
+            c3.last_path = "hip-%s-chain" % p3.kind
             if dsarg is not None:
-                blk.downsample[0].last_path = "hip-%s-chain" % dkind
+                blk.downsample[0].last_path = "hip-%s-chain" % dsplan.kind
             nt1 = None
             if nxtarg is not None:
-                nxt.conv1.last_path = "hip-%s-chain" % p1[4]
-                nt1 = Act(q=yq1, amax=ctx.range_tensor(nxt.conv1), rng=nxtarg[3])
+                nxt.conv1.last_path = "hip-%s-chain" % p1.kind
+                nt1 = Act(q=yq1, amax=ctx.range_tensor(nxt.conv1), rng=nxtarg.rng)
             return Act(q=yq3, amax=am3, rng=rng3), nt1
         return run_conv(blk.conv3, blk.bn3, t2, True, residual=identity, ctx=ctx, want_amax=out_amax,
                         want_f32=last), None
@@ -419,27 +431,17 @@ def block_forward(blk, x, ctx=None, last=False, t1=None, nxt=None):
 
 
 def stem_s2d_plan(conv, bn):
-    """(codes, col_scale, col_shift, kind) of the stem in space-to-depth form (ops.stem_conv_s2d), or
+    """The StemPlan of the stem in space-to-depth form (ops.stem_conv_s2d), or
     None when conv1 is not the 7x7/2/3 stem on <= 4 channels. Its fp32 weights become per-channel
     fixed point with max(2, L) limbs (quantized channels, if any: exact codes), as in
     QConv2d.packed_s2d."""
     if not (isinstance(conv, QConv2d) and conv.s2d_stem()):
         return None
-    key = (conv._pack_key(), _bn_key(bn), None if conv.bias is None else (conv.bias.data_ptr(), conv.bias._version))
-    cache = getattr(conv, "_s2d_cache", None)
-    if cache is not None and cache[0] == key:
-        return cache[1]
-    with torch.no_grad():
+
+    def build():
         codes, wscale, kind = conv.packed_s2d()
-        if bn is not None:
-            a, b = _bn_fold(bn)
-        else:
-            a, b = torch.ones_like(wscale), torch.zeros_like(wscale)
-        if conv.bias is not None:
-            b = b + conv.bias.float() * a
-        plan = (codes, (wscale * a).contiguous(), b.contiguous(), kind)
-    conv._s2d_cache = (key, plan)
-    return plan
+        return StemPlan(codes, *_fold(conv, bn, wscale), kind)
+    return _cached_plan(conv, bn, "_s2d_cache", build)
 
 
 def stem_forward(model, x, ctx=None):
@@ -478,10 +480,7 @@ def stem_forward(model, x, ctx=None):
         yam = torch.zeros(n, dtype=torch.float32, device=x.device)
         y = ops.tuned_stem_conv_s2d(xq, amax_in, codes, x.shape[2], x.shape[3], col_scale, col_shift,
                                     relu=True, y_absmax=yam)
-        if ctx is not None and ctx.record is not None:
-            prev = ctx.record.get(id(conv))
-            m = yam.amax().reshape(1)
-            ctx.record[id(conv)] = m if prev is None else torch.maximum(prev, m)
+        _record_max(ctx, conv, yam)
         q, f = ops.maxpool_quantize(y, yam, want_f32=True)
         return Act(f32=f, q=q, amax=yam)
     # a stem the kernel does not cover: the reference's fp32 arithmetic (MIOpen), then quantized
@@ -648,17 +647,43 @@ def _bump_content(model):
             m._content_gen += 1
 
 
+class ModelState:
+    """Everything the engine keeps per model, as ``model._smpq`` (model_state): ``fp`` the last
+    content fingerprint taken, ``dyn`` the dynamic mode's (signature, fingerprinter) or None,
+    ``ranges`` the installed StaticRanges or None, ``graphs`` the GraphCache. ResNet._apply drops
+    it once a tensor was replaced (new_evaluation's flag, model._smpq_recal, outlives that)."""
+    __slots__ = ("fp", "dyn", "ranges", "graphs")
+
+    def __init__(self):
+        self.fp, self.dyn, self.ranges, self.graphs = None, None, None, GraphCache()
+
+
+def model_state(model):
+    return model.__dict__.get("_smpq") or model.__dict__.setdefault("_smpq", ModelState())
+
+
+class StaticRanges:
+    """The installed static ranges of a model (set_calibration): ``by_conv`` {id(conv): range},
+    ``sig`` the model's signature they were installed for, ``tensors`` the per-(conv, n) range
+    tensors the forwards share (Ctx.range_tensor) and ``fp`` the fingerprinter of the content they
+    were calibrated on. Compared by identity; captured graphs are keyed on id(by_conv) (_graph_base)."""
+    __slots__ = ("by_conv", "sig", "tensors", "fp")
+
+    def __init__(self, by_conv, sig, fp):
+        self.by_conv, self.sig, self.tensors, self.fp = by_conv, sig, {}, fp
+
+
 def _refresh_fingerprint(model, device, stale=False):
     """Fingerprint the current content. The content-keyed caches are invalidated only when they
     may hold other content: ``stale`` (a fingerprint check failed) or the content differs from
-    the last fingerprint taken (model._smpq_fp, shared by both range modes; one host sync).
+    the last fingerprint taken (ModelState.fp, shared by both range modes; one host sync).
     Returns (fingerprinter, whether the caches were invalidated)."""
     fp = Fingerprinter(_fp_tensors(model), device)
-    old = getattr(model, "_smpq_fp", None)
-    changed = stale or old is None or not fp.same_content(old)
+    st = model_state(model)
+    changed = stale or st.fp is None or not fp.same_content(st.fp)
     if changed:
         _bump_content(model)
-    model._smpq_fp = fp
+    st.fp = fp
     return fp, changed
 
 
@@ -686,20 +711,21 @@ def set_calibration(model, c, widen=True):
     and unchanged weights (same signature, same content as the previous calibration, e.g. an
     overflow rerun) each range stays at least its previous value, so ranges only grow. Ranges
     equal to the installed ones (same weights, same calibration batch) keep the installed
-    calibration object, and with it the graphs captured for it."""
+    StaticRanges object, and with it the graphs captured for it."""
     maxima = c.maxima.cpu().tolist()
-    old = getattr(model, "_smpq_ranges", None)
-    keep = widen and old is not None and not c.changed and old[1] == c.sig0
+    st = model_state(model)
+    old = st.ranges
+    keep = widen and old is not None and not c.changed and old.sig == c.sig0
     ranges = {}
     for k, v in zip(c.keys, maxima):
         r = max(v, 1e-30) * HEADROOM
-        if keep and k in old[0]:
-            r = max(r, old[0][k])
+        if keep and k in old.by_conv:
+            r = max(r, old.by_conv[k])
         ranges[k] = r
     sig = _signature(model)
-    if old is not None and not c.changed and old[1] == sig and old[0] == ranges:
+    if old is not None and not c.changed and old.sig == sig and old.by_conv == ranges:
         return
-    model._smpq_ranges = (ranges, sig, {}, c.fp)
+    st.ranges = StaticRanges(ranges, sig, c.fp)
 
 
 def calibrate(model, x, stale=False, fresh=False):
@@ -724,21 +750,21 @@ def new_evaluation(model):
 
 
 def _static_eager(model, x, cal):
-    ctx = Ctx(x.shape[0], x.device, ranges=cal[0], cache=cal[2])
+    ctx = Ctx(x.shape[0], x.device, ranges=cal.by_conv, cache=cal.tensors)
     y = _forward(model, x, ctx)
-    cal[3].check(ctx.overflow[1:])
+    cal.fp.check(ctx.overflow[1:])
     return y, ctx.overflow
 
 
 def _graph_base(cal):
     """What every captured graph of a model depends on besides its input's shape and address:
     the calibration (ranges, signature) and the forward's structure knobs."""
-    return (cal[1], CHUNK[0], ops.get_act_limbs(), id(cal[0]), FUSED_STEM[0], CONCURRENT_DS[0], STREAMS[0],
+    return (cal.sig, CHUNK[0], ops.get_act_limbs(), id(cal.by_conv), FUSED_STEM[0], CONCURRENT_DS[0], STREAMS[0],
             ops.KMAJOR[0], PAIR_1X1[0], FUSE_DS[0], FUSE_DS_MAX_CIN[0], PAIR_STAGE_ENTRY[0])
 
 
-def _graph_key(model, x, cal):
-    return (tuple(x.shape), x.dtype, x.device) + _graph_base(cal)
+def _graph_key(x, base):
+    return (tuple(x.shape), x.dtype, x.device) + base
 
 
 def _addr_key(x):
@@ -747,28 +773,113 @@ def _addr_key(x):
     return (tuple(x.shape), x.dtype, x.device, x.data_ptr()) if x.is_contiguous() else None
 
 
-def _graphs(model, cal):
-    """The model's per-address graphs for calibration ``cal`` (dropped when it changes; graphs of
-    other input shapes are kept, so a short last batch does not evict the full-batch graphs)."""
-    per = getattr(model, "_smpq_graphs", None)
-    base = _graph_base(cal)
-    if per is None or per.get("base") != base:
-        per = model._smpq_graphs = {"base": base}
-    return per
-
-
-def _graph_ready(model, x, cal):
-    ak = _addr_key(x)
-    if ak is not None and ak in _graphs(model, cal):
-        return True
-    entry = getattr(model, "_smpq_graph", None)
-    return entry is not None and entry[0] == _graph_key(model, x, cal)
-
-
 # HIP graphs captured on an input tensor's own memory (no copy of the input into the graph's static
 # buffer): up to this many distinct input addresses per model (an evaluation loop's input buffers
 # recycle a few addresses); further inputs are copied into the fallback graph's static buffer.
 GRAPHS_PER_MODEL = [int(_os.environ.get("SMPQ_GRAPHS", "4"))]
+
+
+class GraphEntry:
+    """One captured forward: the graph, its Ctx (a replay writes its overflow flags), its static logits,
+    and the static copy of the input it reads (the fallback) or None (it reads its input's own memory)."""
+    __slots__ = ("graph", "ctx", "logits", "static_x")
+
+    def __init__(self, graph, ctx, logits, static_x=None):
+        self.graph, self.ctx, self.logits, self.static_x = graph, ctx, logits, static_x
+
+    def replay(self, x):
+        if self.static_x is not None:
+            self.static_x.copy_(x)
+        self.graph.replay()
+        stats["graph_replays"] += 1
+        return self.logits.clone(), self.ctx.overflow
+
+
+class GraphCache:
+    """A model's captured graphs: ``entries`` {_addr_key: GraphEntry} captured on their inputs'
+    own memory for ``base`` (_graph_base), one ``fallback`` entry (keyed by shape, dtype, device
+    and base) that reads a static copy of its input, and the memory ``pool`` they all share. It
+    holds the only references to the graph executables, released at these points and no others
+    (forget() is for tests and tools):
+      1. every per-address entry, together, by the first call of ready (contiguous inputs only),
+         lookup, forward or capture_for whose ``base`` differs from the stored one (_sync); entries
+         of other input shapes stay, so a short last batch does not evict the full-batch graphs;
+      2. the fallback entry when capture_for has captured a new fallback (after that capture);
+      3. the fallback entry in forward, before the warming eager forward, when the input has no
+         per-address slot left and the fallback is missing or of another key. While a slot is
+         free it is not touched: a stale fallback then stays alive;
+      4. the pool handle never: it is made once per (model, device) and outlives the graphs;
+      5. everything when ResNet._apply drops the model's state (a tensor was replaced)."""
+    __slots__ = ("base", "entries", "fallback_key", "fallback", "pool_device", "pool")
+
+    def __init__(self):
+        self.pool_device = self.pool = None
+        self.forget()
+
+    def forget(self, fallback=True):
+        self._sync(None)
+        if fallback:
+            self.fallback_key = self.fallback = None
+
+    def _sync(self, base):
+        if base is None or self.base != base:
+            self.base, self.entries = base, {}
+
+    def pool_for(self, device):
+        # one memory pool for all of the model's graphs: they are replayed one at a time on one stream
+        # and each replay's outputs are copied out before the next, so they may share blocks
+        if self.pool is None or self.pool_device != device:
+            self.pool_device, self.pool = device, torch.cuda.graph_pool_handle()
+        return self.pool
+
+    def has_slot(self, x):
+        """Is a per-address slot left for an input of this shape (and is ``x`` contiguous)?"""
+        ak = _addr_key(x)
+        return ak is not None and sum(1 for k in self.entries if k[:3] == ak[:3]) < GRAPHS_PER_MODEL[0]
+
+    def ready(self, x, base):
+        """Does a graph take ``x``: its address's own, or the fallback (replayed only without a free slot)?"""
+        ak = _addr_key(x)
+        if ak is not None:
+            self._sync(base)
+            if ak in self.entries:
+                return True
+        return self.fallback is not None and self.fallback_key == _graph_key(x, base)
+
+    def lookup(self, x, base):
+        """The entry whose replay is the forward of ``x``, or None: run it eagerly, then capture."""
+        self._sync(base)
+        hit = self.entries.get(_addr_key(x))  # (None, a non-contiguous input's key, is never one)
+        if hit is not None or self.has_slot(x) or self.fallback_key != _graph_key(x, base):
+            return hit
+        return self.fallback
+
+    def capture_for(self, x, base, capture):
+        """``capture(x_in)`` -> GraphEntry, on the input's own memory when it has a per-address slot
+        left, otherwise as the fallback graph reading a static copy of the input."""
+        self._sync(base)
+        if self.has_slot(x):
+            self.entries[_addr_key(x)] = capture(x)
+            return
+        static_x = x.contiguous().clone()
+        entry = capture(static_x)
+        entry.static_x = static_x
+        self.fallback_key, self.fallback = _graph_key(x, base), entry
+
+    def forward(self, x, base, eager, capture=None):
+        """(logits, overflow flag tensor) of ``x``: the replay of its address's own graph, which
+        reads the input where it lies, or of the fallback on a copy of it in the static buffer.
+        Without a graph for ``x`` the forward runs eagerly (``eager()``), and the graph is captured
+        right after it (``capture``, unless a range overflowed)."""
+        entry = self.lookup(x, base)
+        if entry is not None:
+            return entry.replay(x)
+        if not self.has_slot(x):
+            self.fallback_key = self.fallback = None
+        y, ovf = eager()  # warm every cache outside the capture
+        if capture is not None and not any(ovf.tolist()):
+            self.capture_for(x, base, capture)
+        return y, ovf
 
 
 # Held while a HIP graph is being captured. torch captures in the default "global" mode, in which
@@ -780,78 +891,39 @@ CAPTURE_LOCK = threading.Lock()
 
 
 def _capture(model, x_in, cal):
+    """What every capture shares (under CAPTURE_LOCK); what is enqueued inside it is _capture_body's."""
     with CAPTURE_LOCK:
-        return _capture_locked(model, x_in, cal)
+        g = torch.cuda.CUDAGraph()
+        ctx = Ctx(x_in.shape[0], x_in.device, ranges=cal.by_conv, cache=cal.tensors)
+        pool = model_state(model).graphs.pool_for(x_in.device)
+        torch.cuda.synchronize()
+        # thread_local: only THIS thread's unsafe calls break the capture; other threads' CUDA calls
+        # (a DataLoader's pin-memory thread allocating pinned host memory, ADVICE r5) stay legal
+        with torch.cuda.graph(g, pool=pool, capture_error_mode="thread_local"):
+            ctx.overflow = torch.zeros(2, dtype=torch.int32, device=x_in.device)
+            y_static = _capture_body(model, x_in, ctx, cal.fp)
+        stats["graph_captures"] += 1
+        return GraphEntry(g, ctx, y_static)
 
 
-def _capture_locked(model, x_in, cal):
-    g = torch.cuda.CUDAGraph()
-    ctx = Ctx(x_in.shape[0], x_in.device, ranges=cal[0], cache=cal[2])
-    # one memory pool for all of the model's graphs: they are replayed one at a time on one stream
-    # and each replay's outputs are copied out before the next, so they may share blocks
-    pool = getattr(model, "_smpq_pool", None)
-    if pool is None or pool[0] != x_in.device:
-        pool = model._smpq_pool = (x_in.device, torch.cuda.graph_pool_handle())
-    torch.cuda.synchronize()
-    # thread_local: only THIS thread's unsafe calls break the capture; other threads' CUDA calls
-    # (a DataLoader's pin-memory thread allocating pinned host memory) stay legal
-    with torch.cuda.graph(g, pool=pool[1], capture_error_mode="thread_local"):
-        ctx.overflow = torch.zeros(2, dtype=torch.int32, device=x_in.device)
-        ctx.pending_check = lambda: cal[3].check(ctx.overflow[1:])
-        y_static = _forward(model, x_in, ctx)
-        if ctx.pending_check is not None:  # (not enqueued inside a batch slice)
-            ctx.pending_check()
-            ctx.pending_check = None
-    stats["graph_captures"] += 1
-    return g, ctx, y_static
-
-
-def _capture_graph_for(model, x, cal):
-    """Capture the static forward of ``x`` (every cache already warm: an eager forward of the same
-    calibration ran first): on the input's own memory when it has a per-address slot left,
-    otherwise as the fallback graph reading a static copy of the input."""
-    per_ptr = _graphs(model, cal)
-    ak = _addr_key(x)
-    same_shape = sum(1 for k in per_ptr if k != "base" and k[:3] == ak[:3]) if ak is not None else 0
-    if ak is not None and same_shape < GRAPHS_PER_MODEL[0]:
-        per_ptr[ak] = _capture(model, x, cal)
-        return
-    static_x = x.contiguous().clone()
-    g, ctx, y_static = _capture(model, static_x, cal)
-    model._smpq_graph = (_graph_key(model, x, cal), g, static_x, ctx, y_static)
+def _capture_body(model, x_in, ctx, fp):
+    """The captured work: the forward, with the weights' content check where _forward places it
+    (tests and tools swap this function to capture other stream topologies)."""
+    ctx.pending_check = lambda: fp.check(ctx.overflow[1:])
+    y_static = _forward(model, x_in, ctx)
+    if ctx.pending_check is not None:  # (not enqueued inside a batch slice)
+        ctx.pending_check()
+        ctx.pending_check = None
+    return y_static
 
 
 def _graph_forward(model, x, cal, capture=True):
-    """Static forward through a captured HIP graph; returns (logits, overflow flag tensor). The
-    graph reads the input where it lies when its (contiguous) input's address has a graph of its
-    own (captured on first sight, up to GRAPHS_PER_MODEL addresses per input shape, dropped with
-    the calibration); otherwise the input is copied into the fallback graph's static buffer.
-    Without a graph for ``x`` the forward runs eagerly, and the graph is captured right after it
-    (``capture``) or left to the caller (``_capture_graph_for``, once a data-parallel group has
-    agreed that this calibration stays)."""
-    key = _graph_key(model, x, cal)
-    per_ptr = _graphs(model, cal)
-    ak = _addr_key(x)
-    hit = per_ptr.get(ak) if ak is not None else None
-    if hit is not None:
-        g, ctx, y_static = hit
-        g.replay()
-        stats["graph_replays"] += 1
-        return y_static.clone(), ctx.overflow
-    same_shape = sum(1 for k in per_ptr if k != "base" and k[:3] == ak[:3]) if ak is not None else 0
-    entry = getattr(model, "_smpq_graph", None)
-    if (ak is not None and same_shape < GRAPHS_PER_MODEL[0]) or entry is None or entry[0] != key:
-        if not (ak is not None and same_shape < GRAPHS_PER_MODEL[0]):
-            model._smpq_graph = None
-        y, ovf = _static_eager(model, x, cal)  # warm every cache outside the capture
-        if capture and not any(ovf.tolist()):
-            _capture_graph_for(model, x, cal)
-        return y, ovf
-    _, g, static_x, ctx, y_static = entry
-    static_x.copy_(x)
-    g.replay()
-    stats["graph_replays"] += 1
-    return y_static.clone(), ctx.overflow
+    """Static forward through a captured HIP graph (GraphCache.forward); ``capture`` False leaves
+    the capture to the caller (``GraphCache.capture_for``, once a data-parallel group has agreed
+    that this calibration stays)."""
+    return model_state(model).graphs.forward(
+        x, _graph_base(cal), lambda: _static_eager(model, x, cal),
+        (lambda x_in: _capture(model, x_in, cal)) if capture else None)
 
 
 def _dynamic_forward(model, x):
@@ -860,17 +932,17 @@ def _dynamic_forward(model, x):
     change seen again after that (weights written concurrently with the forward) raises."""
     for attempt in range(2):
         sig = _signature(model)
-        st = getattr(model, "_smpq_dyn", None)
-        if st is None or st[0] != sig or attempt:
+        st = model_state(model)
+        if st.dyn is None or st.dyn[0] != sig or attempt:
             fp, _ = _refresh_fingerprint(model, x.device, stale=attempt > 0)
-            model._smpq_dyn = st = (_signature(model), fp)
+            st.dyn = (_signature(model), fp)
         y = _forward(model, x, None)
         flag = torch.zeros(1, dtype=torch.int32, device=x.device)
-        st[1].check(flag)
+        st.dyn[1].check(flag)
         if int(flag.item()) == 0:
             return y
         stats["stale_reruns"] += 1
-        model._smpq_dyn = None
+        st.dyn = None
     raise RuntimeError("smpq: the model's weights changed while its forward ran (twice); no stale result returned")
 
 
@@ -883,7 +955,8 @@ def forward_fused(model, x):
         # the overflow / staleness flags need a host read after the forward
         raise RuntimeError("smpq: the static-range forward cannot run inside a caller's graph capture "
                            "(it replays its own HIP graph); use dynamic range mode to capture it")
-    cal = getattr(model, "_smpq_ranges", None)
+    st = model_state(model)
+    cal = st.ranges
     fresh = model.__dict__.pop("_smpq_recal", False)
     if _DP[0] is not None:
         # collective decision: every rank calibrates, or none does; and if any rank starts a new
@@ -896,17 +969,17 @@ def forward_fused(model, x):
         need_local = True
         deferred_capture = False
         if cal is not None and not fresh:
-            if USE_GRAPH[0] and _graph_ready(model, x, cal):
+            if USE_GRAPH[0] and st.graphs.ready(x, _graph_base(cal)):
                 y, ovf = _graph_forward(model, x, cal)
-                need_local = _signature(model) != cal[1]
-            elif cal[1] == _signature(model):
+                need_local = _signature(model) != cal.sig
+            elif cal.sig == _signature(model):
                 # no graph for this input yet: an eager forward only; the capture waits until the
                 # ranks have agreed below that this calibration stays (a capture that
                 # another rank's calibration would discard is not paid for)
                 need_local = False
                 y, ovf = _graph_forward(model, x, cal, capture=False) if USE_GRAPH[0] else \
                     _static_eager(model, x, cal)
-                deferred_capture = USE_GRAPH[0] and not _graph_ready(model, x, cal)
+                deferred_capture = USE_GRAPH[0] and not st.graphs.ready(x, _graph_base(cal))
         flags = torch.zeros(4, dtype=torch.int32, device=x.device)
         if ovf is not None:
             flags[:2].copy_(ovf)
@@ -919,21 +992,22 @@ def forward_fused(model, x):
             return calibrate(model, x, stale=bool(stale), fresh=bool(fresh_any))
         if not overflow and not stale:
             if deferred_capture:
-                _capture_graph_for(model, x, cal)
+                # (every cache is warm: the eager forward of this calibration ran above)
+                st.graphs.capture_for(x, _graph_base(cal), lambda x_in: _capture(model, x_in, cal))
             return y
         stats["stale_reruns" if stale else "overflow_reruns"] += 1
         return calibrate(model, x, stale=bool(stale))
     else:
         if cal is None or fresh:
             return calibrate(model, x, fresh=fresh)
-        if USE_GRAPH[0] and _graph_ready(model, x, cal):
+        if USE_GRAPH[0] and st.graphs.ready(x, _graph_base(cal)):
             # fast path: replay first, then validate on the host while the GPU runs; a changed
             # weight or BN buffer discards the result (recalibrate + recapture): nothing stale
             y, ovf = _graph_forward(model, x, cal)
-            if _signature(model) != cal[1]:
+            if _signature(model) != cal.sig:
                 return calibrate(model, x)
         else:
-            if cal[1] != _signature(model):
+            if cal.sig != _signature(model):
                 return calibrate(model, x)
             y, ovf = _graph_forward(model, x, cal) if USE_GRAPH[0] else _static_eager(model, x, cal)
     overflow, stale = ovf.tolist()  # one sync: results are never silently clamped or stale

@@ -179,8 +179,7 @@ class ResNet(nn.Module):
         before = tensors()
         out = super()._apply(fn, *args, **kwargs)
         if tensors() != before:
-            for k in ("_smpq_graph", "_smpq_graphs", "_smpq_dyn", "_smpq_ranges", "_smpq_fp", "_smpq_pool"):
-                self.__dict__.pop(k, None)
+            self.__dict__.pop("_smpq", None)  # engine.ModelState
         return out
 
 

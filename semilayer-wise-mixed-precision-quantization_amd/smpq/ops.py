@@ -4,6 +4,7 @@ Every function validates shapes/dtypes/devices on the host before launching, so 
 never sees an operand that disagrees with its grid (no device-side faults on bad input).
 """
 import os
+from collections import namedtuple
 
 import torch
 
@@ -32,6 +33,36 @@ def get_act_limbs():
 def _req(cond, msg):
     if not cond:
         raise ValueError("smpq: " + msg)
+
+
+def _launch(dev, name, *args):
+    """Call the C-ABI entry ``name`` with ``args`` (a tensor as its address, None as the null pointer:
+    ctypes takes both for a pointer argument) + torch's current stream on ``dev``; raises
+    _lib.SmpqError ("name failed (rc): ...") unless it returns SMPQ_OK."""
+    args = [a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args]
+    with torch.cuda.device(dev):
+        _lib.check(getattr(_lib.load(), name)(*args, _lib.stream_ptr()), name)
+
+
+def _launch_twin(t, name, *args):
+    """_launch of ``name`` for a device tensor ``t``; for a host tensor its native host twin
+    ``name``_host: the same arguments as host addresses, no device and no stream."""
+    if t.is_cuda:
+        return _launch(t.device, name, *args)
+    args = [a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args]
+    _lib.check(getattr(_lib.load(), name + "_host")(*args), name + "_host")
+
+
+# bytes per plane the kernel's 32-bit buffer offsets address (csrc/conv_glds.hip glds_planes_ok)
+PLANE_LIMIT = 0x7fffff00
+
+
+def _image_chunks(n, per_img, what):
+    """The (i0, i1) image ranges a batch of ``n`` runs in when a plane (``per_img`` bytes per image)
+    would pass PLANE_LIMIT (every image is independent: the result of one launch), else None."""
+    nchunk = PLANE_LIMIT // per_img
+    _req(nchunk >= 1, "%s: one image's planes exceed 2 GiB" % what)
+    return [(i0, min(n, i0 + nchunk)) for i0 in range(0, n, nchunk)] if n > nchunk else None
 
 
 # Rounding semantics of functions.py:41 `t / scale` (include/smpq.h SMPQ_QSEM_*): torch on the CPU
@@ -81,10 +112,7 @@ def quantize_channels_(w2d, bits, semantics=None):
         bits_d = bits_t.to(w2d.device)
         step = torch.zeros(cout, dtype=torch.float32, device=w2d.device)
         status = torch.zeros(1, dtype=torch.int32, device=w2d.device)
-        with torch.cuda.device(w2d.device):
-            _lib.check(lib.smpq_quantize_channels_ex(_lib.ptr(w2d), cout, k, _lib.ptr(bits_d),
-                                                     _lib.ptr(step), _lib.ptr(status), sem,
-                                                     _lib.stream_ptr()), "smpq_quantize_channels_ex")
+        _launch(w2d.device, "smpq_quantize_channels_ex", w2d, cout, k, bits_d, step, status, sem)
         bad = int(status.item())  # one sync: the reference raises synchronously
         if bad:
             raise ZeroDivisionError("float division by zero (constant channel %d)" % (bad - 1))
@@ -108,11 +136,7 @@ def pack_weights(w, step):
     codes = torch.empty(cout, kh * kw * cin, dtype=torch.int8, device=w.device)
     offset = torch.empty(cout, dtype=torch.int32, device=w.device)
     status = torch.zeros(2, dtype=torch.int32, device=w.device)
-    lib = _lib.load()
-    with torch.cuda.device(w.device):
-        _lib.check(lib.smpq_pack_weights(_lib.ptr(w), cout, cin, kh, kw, _lib.ptr(step), _lib.ptr(codes),
-                                         _lib.ptr(offset), _lib.ptr(status), _lib.stream_ptr()),
-                   "smpq_pack_weights")
+    _launch(w.device, "smpq_pack_weights", w, cout, cin, kh, kw, step, codes, offset, status)
     return codes, offset, status
 
 
@@ -133,11 +157,7 @@ def pack_weights_ex(w, step, wlimbs):
     offset = torch.zeros(cout, dtype=torch.int32, device=w.device)
     wscale = torch.empty(cout, dtype=torch.float32, device=w.device)
     status = torch.zeros(3, dtype=torch.int32, device=w.device)
-    lib = _lib.load()
-    with torch.cuda.device(w.device):
-        _lib.check(lib.smpq_pack_weights_ex(_lib.ptr(w), cout, cin, kh, kw, _lib.ptr(step), int(wlimbs),
-                                            _lib.ptr(codes), _lib.ptr(offset), _lib.ptr(wscale), _lib.ptr(status),
-                                            _lib.stream_ptr()), "smpq_pack_weights_ex")
+    _launch(w.device, "smpq_pack_weights_ex", w, cout, cin, kh, kw, step, int(wlimbs), codes, offset, wscale, status)
     if KMAJOR[0]:
         # the K-major copy the LDS-DMA tiles stage their weight pieces from (whole cache lines);
         # it lives and dies with these codes
@@ -157,10 +177,7 @@ def weights_kmajor(codes):
     _req(codes.is_cuda and codes.dtype == torch.int8 and codes.is_contiguous() and K % 64 == 0,
          "weights_kmajor: need contiguous int8 [LW, cout, K] with K % 64 == 0")
     out = torch.empty(wl, K // 64, cout, 64, dtype=torch.int8, device=codes.device)
-    lib = _lib.load()
-    with torch.cuda.device(codes.device):
-        _lib.check(lib.smpq_weights_kmajor(_lib.ptr(codes), int(wl), int(cout), int(K), _lib.ptr(out),
-                                           _lib.stream_ptr()), "smpq_weights_kmajor")
+    _launch(codes.device, "smpq_weights_kmajor", codes, int(wl), int(cout), int(K), out)
     return out
 
 
@@ -175,10 +192,7 @@ def image_quantize_s2d(x, x_absmax, limbs=None):
     _req(h >= 2 and w >= 2, "image_quantize_s2d: h and w must be >= 2")
     _req(x_absmax.numel() == n and x_absmax.dtype == torch.float32, "image_quantize_s2d: absmax")
     out = torch.empty(limbs, n, (h + 1) // 2, (w + 1) // 2, 16, dtype=torch.int8, device=x.device)
-    lib = _lib.load()
-    with torch.cuda.device(x.device):
-        _lib.check(lib.smpq_image_quantize_s2d(_lib.ptr(x), n, c, h, w, _lib.ptr(x_absmax), int(limbs),
-                                               _lib.ptr(out), _lib.stream_ptr()), "smpq_image_quantize_s2d")
+    _launch(x.device, "smpq_image_quantize_s2d", x, n, c, h, w, x_absmax, int(limbs), out)
     return out
 
 
@@ -198,11 +212,7 @@ def pack_weights_s2d(w, wlimbs, step=None):
     if step is not None:
         step = step.to(device=w.device, dtype=torch.float32).contiguous()
         _req(step.numel() == cout, "pack_weights_s2d: step length")
-    lib = _lib.load()
-    with torch.cuda.device(w.device):
-        _lib.check(lib.smpq_pack_weights_s2d_ex(_lib.ptr(w), cout, cin, _lib.ptr(step), int(wlimbs), _lib.ptr(codes),
-                                                _lib.ptr(wscale), _lib.ptr(status), _lib.stream_ptr()),
-                   "smpq_pack_weights_s2d_ex")
+    _launch(w.device, "smpq_pack_weights_s2d_ex", w, cout, cin, step, int(wlimbs), codes, wscale, status)
     return codes, wscale
 
 
@@ -225,13 +235,10 @@ def stem_conv_s2d(xq, x_absmax, codes, h, w, col_scale, col_shift, relu=True, y_
         yq = torch.empty(limbs, n, ho, wo, cout, dtype=torch.int8, device=xq.device)
     per_img = max(limbs * h2 * w2 * 16, (4 if want_f32 else 0) * ho * wo * cout,
                   (limbs if yq is not None else 0) * ho * wo * cout)
-    nchunk = PLANE_LIMIT // per_img
-    _req(nchunk >= 1, "stem_conv_s2d: one image's planes exceed 2 GiB")
-    if n > nchunk:
-        # 32-bit plane offsets in the kernel: the images in chunks, as conv2d_q does (every image
-        # is independent, so the result is that of one launch)
-        for i0 in range(0, n, nchunk):
-            i1 = min(n, i0 + nchunk)
+    chunks = _image_chunks(n, per_img, "stem_conv_s2d")
+    if chunks:
+        # 32-bit plane offsets in the kernel: the images in chunks, as conv2d_q does
+        for i0, i1 in chunks:
             r = stem_conv_s2d(xq[:, i0:i1].contiguous(), x_absmax[i0:i1], codes, h, w, col_scale, col_shift, relu,
                               None if y_absmax is None else y_absmax[i0:i1], tile_cfg, emit_range, overflow, want_f32)
             if emit_range is None:
@@ -241,15 +248,11 @@ def stem_conv_s2d(xq, x_absmax, codes, h, w, col_scale, col_shift, relu=True, y_
                     y[i0:i1].copy_(r[0])
                 yq[:, i0:i1].copy_(r[1])
         return y if emit_range is None else (y, yq)
-    lib = _lib.load()
     hook = _CONV_HOOK[0]
     if hook is not None:
         hook.begin()
-    with torch.cuda.device(xq.device):
-        _lib.check(lib.smpq_stem_conv_s2d_q(
-            _lib.ptr(xq), _lib.ptr(x_absmax), n, h, w, _lib.ptr(codes), int(wlimbs), cout, _lib.ptr(col_scale),
-            _lib.ptr(col_shift), 1 if relu else 0, int(limbs), _lib.ptr(y), _lib.ptr(y_absmax), _lib.ptr(yq),
-            float(emit_range or 0.0), _lib.ptr(overflow), int(tile_cfg), _lib.stream_ptr()), "smpq_stem_conv_s2d_q")
+    _launch(xq.device, "smpq_stem_conv_s2d_q", xq, x_absmax, n, h, w, codes, int(wlimbs), cout, col_scale, col_shift,
+            1 if relu else 0, int(limbs), y, y_absmax, yq, float(emit_range or 0.0), overflow, int(tile_cfg))
     if hook is not None:
         hook.end(alg_work(n, h, w, 3, cout, 7, 7, ho, wo, limbs, wlimbs, y is not None, yq is not None, False, False))
     return y if emit_range is None else (y, yq)
@@ -287,15 +290,11 @@ def stem_pool_s2d(xq, x_absmax, codes, h, w, col_scale, col_shift, emit_range, o
     _req(K == 256, "stem_pool_s2d: codes must come from pack_weights_s2d")
     _req(overflow is not None and emit_range is not None, "stem_pool_s2d: needs an output range and an overflow flag")
     yq = torch.empty(limbs, n, h // 4, w // 4, cout, dtype=torch.int8, device=xq.device)
-    lib = _lib.load()
     hook = _CONV_HOOK[0]
     if hook is not None:
         hook.begin()
-    with torch.cuda.device(xq.device):
-        _lib.check(lib.smpq_stem_pool_s2d_q(
-            _lib.ptr(xq), _lib.ptr(x_absmax), n, h, w, _lib.ptr(codes), int(wlimbs), cout, _lib.ptr(col_scale),
-            _lib.ptr(col_shift), int(limbs), _lib.ptr(yq), float(emit_range), _lib.ptr(overflow),
-            _lib.stream_ptr()), "smpq_stem_pool_s2d_q")
+    _launch(xq.device, "smpq_stem_pool_s2d_q", xq, x_absmax, n, h, w, codes, int(wlimbs), cout, col_scale, col_shift,
+            int(limbs), yq, float(emit_range), overflow)
     if hook is not None:
         work = alg_work(n, h, w, 3, cout, 7, 7, h // 2, w // 2, limbs, wlimbs, False, False, False, False)
         work["bytes"] += limbs * n * (h // 4) * (w // 4) * cout  # the pooled output, written once
@@ -311,10 +310,7 @@ def maxpool_limbs(xq):
     _req(xq.is_cuda and xq.dtype == torch.int8 and xq.is_contiguous() and c % 16 == 0, "maxpool_limbs: planes")
     ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
     out = torch.empty(limbs, n, ho, wo, c, dtype=torch.int8, device=xq.device)
-    lib = _lib.load()
-    with torch.cuda.device(xq.device):
-        _lib.check(lib.smpq_maxpool_limbs(_lib.ptr(xq), n, h, w, c, int(limbs), _lib.ptr(out), _lib.stream_ptr()),
-                   "smpq_maxpool_limbs")
+    _launch(xq.device, "smpq_maxpool_limbs", xq, n, h, w, c, int(limbs), out)
     return out
 
 
@@ -329,10 +325,7 @@ def maxpool_quantize(x_nhwc, x_absmax, limbs=None, want_f32=True):
     ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
     q = torch.empty(limbs, n, ho, wo, c, dtype=torch.int8, device=x_nhwc.device)
     f = torch.empty(n, ho, wo, c, dtype=torch.float32, device=x_nhwc.device) if want_f32 else None
-    lib = _lib.load()
-    with torch.cuda.device(x_nhwc.device):
-        _lib.check(lib.smpq_maxpool_quantize(_lib.ptr(x_nhwc), n, h, w, c, _lib.ptr(x_absmax), int(limbs), _lib.ptr(q),
-                                             _lib.ptr(f), _lib.stream_ptr()), "smpq_maxpool_quantize")
+    _launch(x_nhwc.device, "smpq_maxpool_quantize", x_nhwc, n, h, w, c, x_absmax, int(limbs), q, f)
     return q, f
 
 
@@ -345,10 +338,7 @@ def act_absmax(x_nhwc, out=None):
         out = torch.zeros(n, dtype=torch.float32, device=x_nhwc.device)
     _req(out.numel() == n and out.dtype == torch.float32 and out.is_contiguous(), "act_absmax: out")
     per = x_nhwc.numel() // n
-    lib = _lib.load()
-    with torch.cuda.device(x_nhwc.device):
-        _lib.check(lib.smpq_act_absmax(_lib.ptr(x_nhwc), n, per, _lib.ptr(out), _lib.stream_ptr()),
-                   "smpq_act_absmax")
+    _launch(x_nhwc.device, "smpq_act_absmax", x_nhwc, n, per, out)
     return out
 
 
@@ -363,10 +353,7 @@ def act_quantize(x, x_absmax, limbs=None, out=None):
     if out is None:
         out = torch.empty((limbs,) + tuple(x.shape), dtype=torch.int8, device=x.device)
     _req(out.shape == (limbs,) + tuple(x.shape) and out.dtype == torch.int8 and out.is_contiguous(), "act_quantize: out")
-    lib = _lib.load()
-    with torch.cuda.device(x.device):
-        _lib.check(lib.smpq_act_quantize(_lib.ptr(x), n, per, _lib.ptr(x_absmax), int(limbs), _lib.ptr(out),
-                                         _lib.stream_ptr()), "smpq_act_quantize")
+    _launch(x.device, "smpq_act_quantize", x, n, per, x_absmax, int(limbs), out)
     return out
 
 
@@ -457,13 +444,10 @@ def conv2d_q(xq, x_absmax, codes, offset, kh, kw, stride, pad, col_scale, col_sh
         _req(y_absmax.numel() == n and y_absmax.dtype == torch.float32, "conv: y_absmax")
     per_img = max(limbs * h * w * cin, (limbs if (yq is not None or residual_q is not None) else 0) * ho * wo * cout,
                   (4 if (out is not None or residual is not None) else 0) * ho * wo * cout)
-    nchunk = PLANE_LIMIT // per_img
-    _req(nchunk >= 1, "conv: one image's planes exceed 2 GiB")
-    if n > nchunk:
-        # the kernel addresses each plane with 32-bit offsets: run the images in chunks (every
-        # image is independent, so the result is the same as one launch)
-        for i0 in range(0, n, nchunk):
-            i1 = min(n, i0 + nchunk)
+    chunks = _image_chunks(n, per_img, "conv")
+    if chunks:
+        # the kernel addresses each plane with 32-bit offsets: run the images in chunks
+        for i0, i1 in chunks:
             r = conv2d_q(xq[:, i0:i1].contiguous(), x_absmax[i0:i1], codes, offset, kh, kw, stride, pad,
                          col_scale, col_shift, residual=None if residual is None else residual[i0:i1], relu=relu,
                          y_absmax=None if y_absmax is None else y_absmax[i0:i1],
@@ -474,30 +458,20 @@ def conv2d_q(xq, x_absmax, codes, offset, kh, kw, stride, pad, col_scale, col_sh
             if yq is not None:
                 yq[:, i0:i1].copy_(r[1])
         return (out, yq) if emit_range is not None else out
-    lib = _lib.load()
     hook = _CONV_HOOK[0]
     if hook is not None:
         hook.begin()
-    with torch.cuda.device(xq.device):
-        if km is not None:
-            _req(km.shape == (wlimbs, K // 64, cout, 64) and km.device == xq.device, "conv: K-major codes")
-        _lib.check(lib.smpq_conv2d_fwd_q_km(
-            _lib.ptr(xq), _lib.ptr(x_absmax), n, h, w, cin, _lib.ptr(codes), _lib.ptr(km), int(wlimbs),
-            _lib.ptr(offset), cout,
-            kh, kw, stride, pad, _lib.ptr(col_scale), _lib.ptr(col_shift), _lib.ptr(residual), 1 if relu else 0,
-            int(limbs), _lib.ptr(out), _lib.ptr(y_absmax), _lib.ptr(yq), float(emit_range or 0.0),
-            _lib.ptr(overflow), _lib.ptr(residual_q), float(residual_range or 0.0), int(tile_cfg),
-            _lib.stream_ptr()), "smpq_conv2d_fwd_q_km")
+    if km is not None:
+        _req(km.shape == (wlimbs, K // 64, cout, 64) and km.device == xq.device, "conv: K-major codes")
+    _launch(xq.device, "smpq_conv2d_fwd_q_km", xq, x_absmax, n, h, w, cin, codes, km, int(wlimbs), offset, cout, kh, kw,
+            stride, pad, col_scale, col_shift, residual, 1 if relu else 0, int(limbs), out, y_absmax, yq,
+            float(emit_range or 0.0), overflow, residual_q, float(residual_range or 0.0), int(tile_cfg))
     if hook is not None:
         hook.end(alg_work(n, h, w, cin, cout, kh, kw, ho, wo, limbs, wlimbs, out is not None, yq is not None,
                           residual is not None, residual_q is not None))
     if emit_range is not None:
         return out, yq
     return out
-
-
-# bytes per plane the kernel's 32-bit buffer offsets address (csrc/conv_glds.hip glds_planes_ok)
-PLANE_LIMIT = 0x7fffff00
 
 
 def conv_pair_supported(cin, cout1, cout2, limbs=3):
@@ -524,30 +498,37 @@ def _one_limb(codes, what):
     return codes[0] if codes.dim() == 3 else codes
 
 
+# conv_chain_q's fused downsample: its input limb planes and their per-image range, its codes
+# [3, cout1, ds_cin], folded scale and shift, static output range and stride; and its chained next
+# conv1: codes, folded scale and shift, static output range
+ChainDs = namedtuple("ChainDs", "xq x_absmax codes col_scale col_shift rng stride", defaults=(1,))
+ChainNext = namedtuple("ChainNext", "codes col_scale col_shift rng")
+
+
 def conv_chain_q(xq, x_absmax, codes1, offset1, col_scale1, col_shift1, emit_range1, y1_absmax, overflow,
                  residual_q=None, residual_range=None, ds=None, nxt=None):
     """A Bottleneck's conv3 (1x1 + folded BN + identity + ReLU, exact codes, optional weight offsets)
     in one launch with (csrc/conv_resident.hip, smpq_conv2d_chain_fwd):
-      - its identity: ``residual_q`` limb planes (+ ``residual_range``), or ``ds`` = (ds_xq,
-        ds_x_absmax, ds_codes [3, cout1, ds_cin], ds_col_scale, ds_col_shift, ds_range[, ds_stride]):
-        the block's 1x1 downsample (stride 1 by default) over conv3's output pixels, computed in the
-        same tiles (its output codes feed the residual; never written);
-      - ``nxt`` = (codes2, col_scale2, col_shift2, emit_range2): the next block's conv1 (ReLU) on
+      - its identity: ``residual_q`` limb planes (+ ``residual_range``), or ``ds`` (a ChainDs, or its
+        fields as a plain tuple): the block's 1x1 downsample (stride 1 by default) over conv3's
+        output pixels, computed in the same tiles (its output codes feed the residual; never written);
+      - ``nxt`` (a ChainNext, or its fields as a plain tuple): the next block's conv1 (ReLU) on
         conv3's output tile.
     Returns (yq1, yq2 or None), bitwise what the separate launches write; ``overflow`` covers every
     output of the chain (the downsample's included)."""
+    ds = None if ds is None else ChainDs(*ds)
+    nxt = None if nxt is None else ChainNext(*nxt)
     _req(xq.is_cuda and xq.dtype == torch.int8 and xq.dim() == 5 and xq.is_contiguous(), "chain: xq")
     limbs, n, h, w, cin = xq.shape
     c1 = _one_limb(codes1, "conv3")
     cout1 = c1.shape[0]
-    c2 = _one_limb(nxt[0], "conv1") if nxt is not None else None
+    c2 = _one_limb(nxt.codes, "conv1") if nxt is not None else None
     cout2 = c2.shape[0] if c2 is not None else 0
     _req(c1.shape == (cout1, cin) and c1.is_contiguous() and c1.dtype == torch.int8, "chain: conv3 codes")
     _req(c2 is None or (c2.shape == (cout2, cout1) and c2.is_contiguous() and c2.dtype == torch.int8),
          "chain: conv1 codes")
-    ds_stride = int(ds[6]) if (ds is not None and len(ds) > 6) else 1
     if ds is not None:
-        _req(cout2 == 0 and conv_chain_ds_supported(cin, cout1, ds[0].shape[-1], ds_stride, limbs),
+        _req(cout2 == 0 and conv_chain_ds_supported(cin, cout1, ds.xq.shape[-1], int(ds.stride), limbs),
              "chain: shape not built")
     else:
         _req(conv_chain_supported(cin, cout1, cout2, limbs), "chain: shape not built")
@@ -557,67 +538,58 @@ def conv_chain_q(xq, x_absmax, codes1, offset1, col_scale1, col_shift1, emit_ran
         _req(residual_q.shape == (limbs, n, h, w, cout1) and residual_q.dtype == torch.int8
              and residual_q.is_contiguous() and residual_range is not None and residual_range > 0, "chain: residual_q")
     vecs = [(col_scale1, cout1), (col_shift1, cout1)]
+    dh = dw = dcin = 0
     if ds is not None:
-        dxq, dam, dcodes, dcs, dsh, drng = ds[:6]
+        dxq, ds_stride = ds.xq, int(ds.stride)
         _, _, dh, dw, dcin = dxq.shape
         _req(dxq.dim() == 5 and dxq.shape[:2] == (limbs, n) and (dh - 1) // ds_stride + 1 == h
              and (dw - 1) // ds_stride + 1 == w and dxq.dtype == torch.int8 and dxq.is_contiguous()
-             and dam.numel() == n, "chain: downsample input (its output pixels must be conv3's)")
-        _req(dcodes.shape == (3, cout1, dcin) and dcodes.dtype == torch.int8 and dcodes.is_contiguous(),
+             and ds.x_absmax.numel() == n, "chain: downsample input (its output pixels must be conv3's)")
+        _req(ds.codes.shape == (3, cout1, dcin) and ds.codes.dtype == torch.int8 and ds.codes.is_contiguous(),
              "chain: downsample codes [3, cout, ds_cin]")
-        _req(drng > 0, "chain: downsample range")
-        vecs += [(dcs, cout1), (dsh, cout1)]
+        _req(ds.rng > 0, "chain: downsample range")
+        vecs += [(ds.col_scale, cout1), (ds.col_shift, cout1)]
     if nxt is not None:
-        vecs += [(nxt[1], cout2), (nxt[2], cout2)]
+        vecs += [(nxt.col_scale, cout2), (nxt.col_shift, cout2)]
         _req(y1_absmax is not None and y1_absmax.numel() == n, "chain: y1_absmax")
     for t, c in vecs:
         _req(t.dtype == torch.float32 and t.numel() == c and t.is_contiguous() and t.device == xq.device,
              "chain: col vectors")
     _req(x_absmax.numel() == n and overflow is not None and overflow.dtype == torch.int32
          and overflow.device == xq.device, "chain: absmax / overflow")
-    nchunk = PLANE_LIMIT // (limbs * max(h * w * max(cin, cout1), 0 if ds is None else ds[0].shape[2] * ds[0].shape[3]
-                                         * ds[0].shape[4]))
-    _req(nchunk >= 1, "chain: one image's planes exceed 2 GiB")
-    if n > nchunk:  # 32-bit buffer offsets: image chunks (independent images, the same result)
-        yq1 = torch.empty(limbs, n, h, w, cout1, dtype=torch.int8, device=xq.device)
-        yq2 = torch.empty(limbs, n, h, w, cout2, dtype=torch.int8, device=xq.device) if nxt is not None else None
-        for i0 in range(0, n, nchunk):
-            i1 = min(n, i0 + nchunk)
+    chunks = _image_chunks(n, limbs * max(h * w * max(cin, cout1), dh * dw * dcin), "chain")
+    yq1 = torch.empty(limbs, n, h, w, cout1, dtype=torch.int8, device=xq.device)
+    yq2 = torch.empty(limbs, n, h, w, cout2, dtype=torch.int8, device=xq.device) if nxt is not None else None
+    if chunks:  # 32-bit buffer offsets: image chunks
+        for i0, i1 in chunks:
             a, b = conv_chain_q(
                 xq[:, i0:i1].contiguous(), x_absmax[i0:i1], codes1, offset1, col_scale1, col_shift1, emit_range1,
                 None if y1_absmax is None else y1_absmax[i0:i1], overflow,
                 residual_q=None if residual_q is None else residual_q[:, i0:i1].contiguous(),
                 residual_range=residual_range,
-                ds=None if ds is None else (ds[0][:, i0:i1].contiguous(), ds[1][i0:i1]) + tuple(ds[2:]), nxt=nxt)
+                ds=None if ds is None else ds._replace(xq=dxq[:, i0:i1].contiguous(), x_absmax=ds.x_absmax[i0:i1]),
+                nxt=nxt)
             yq1[:, i0:i1].copy_(a)
             if b is not None:
                 yq2[:, i0:i1].copy_(b)
         return yq1, yq2
-    yq1 = torch.empty(limbs, n, h, w, cout1, dtype=torch.int8, device=xq.device)
-    yq2 = torch.empty(limbs, n, h, w, cout2, dtype=torch.int8, device=xq.device) if nxt is not None else None
-    lib = _lib.load()
     hook = _CONV_HOOK[0]
     if hook is not None:
         hook.begin()
-    P = _lib.ptr
-    with torch.cuda.device(xq.device):
-        _lib.check(lib.smpq_conv2d_chain_fwd(
-            P(xq), P(x_absmax), n, h, w, cin, P(c1), P(offset1), cout1, P(col_scale1), P(col_shift1),
-            P(residual_q), float(residual_range or 0.0),
-            P(ds[0]) if ds else None, P(ds[1]) if ds else None, ds[0].shape[2] if ds else 0,
-            ds[0].shape[3] if ds else 0, ds[0].shape[4] if ds else 0, ds_stride if ds else 0,
-            P(ds[2]) if ds else None, 3 if ds else 0,
-            P(ds[3]) if ds else None, P(ds[4]) if ds else None, float(ds[5]) if ds else 0.0,
-            P(yq1), float(emit_range1), P(y1_absmax),
-            P(c2), cout2, P(nxt[1]) if nxt else None, P(nxt[2]) if nxt else None, P(yq2),
-            float(nxt[3]) if nxt else 0.0, P(overflow), _lib.stream_ptr()), "smpq_conv2d_chain_fwd")
+    # (an absent downsample / next conv: null pointers and zeros)
+    d = ds or ChainDs(None, None, None, None, None, 0.0, 0)
+    nx = nxt or ChainNext(None, None, None, 0.0)
+    _launch(xq.device, "smpq_conv2d_chain_fwd", xq, x_absmax, n, h, w, cin, c1, offset1, cout1, col_scale1, col_shift1,
+            residual_q, float(residual_range or 0.0),
+            d.xq, d.x_absmax, dh, dw, dcin, int(d.stride), d.codes, 3 if ds else 0, d.col_scale, d.col_shift,
+            float(d.rng), yq1, float(emit_range1), y1_absmax,
+            c2, cout2, nx.col_scale, nx.col_shift, yq2, float(nx.rng), overflow)
     if hook is not None:
         # one launch doing every chained conv's work; the reads / writes it removes are not counted
         w1 = alg_work(n, h, w, cin, cout1, 1, 1, h, w, limbs, 1, False, True, False, residual_q is not None)
         ops_, nbytes, shape = w1["ops"], w1["bytes"], "%4d->%4d" % (cin, cout1)
         if ds is not None:
-            wd = alg_work(n, ds[0].shape[2], ds[0].shape[3], ds[0].shape[4], cout1, 1, 1, h, w, limbs, 3, False,
-                          False, False, False)
+            wd = alg_work(n, dh, dw, dcin, cout1, 1, 1, h, w, limbs, 3, False, False, False, False)
             ops_ += wd["ops"]
             nbytes += wd["bytes"]  # the downsample's input and weights (its output never leaves the CU)
             shape += "+ds"
@@ -783,11 +755,12 @@ def tuned_conv2d_q(xq, x_absmax, codes, offset, kh, kw, stride, pad, col_scale, 
     key = (n, h, w, cin, cout, kh, kw, stride, pad, limbs, wlimbs, residual is not None, emit_range is not None,
            want_f32, residual_q is not None)
 
+    args = (xq, x_absmax, codes, offset, kh, kw, stride, pad, col_scale, col_shift)
+    kwargs = dict(residual=residual, relu=relu, y_absmax=y_absmax, out=out, emit_range=emit_range, overflow=overflow,
+               want_f32=want_f32, residual_q=residual_q, residual_range=residual_range)
+
     def run(c):
-        conv2d_q(xq, x_absmax, codes, offset, kh, kw, stride, pad, col_scale, col_shift,
-                 residual=residual, relu=relu, y_absmax=y_absmax, out=out, tile_cfg=c,
-                 emit_range=emit_range, overflow=overflow, want_f32=want_f32,
-                 residual_q=residual_q, residual_range=residual_range)
+        conv2d_q(*args, tile_cfg=c, **kwargs)
     # the halo tiles run only the static-range limb-plane epilogue with ReLU, optionally with a
     # limb-plane residual (stride 1 / pad 1 for now): the key does not carry relu / y_absmax, so
     # other calls of a key never see them
@@ -804,10 +777,7 @@ def tuned_conv2d_q(xq, x_absmax, codes, offset, kh, kw, stride, pad, col_scale, 
     cands = [c for c in tile_configs() if _tile_fits(c, limbs, wlimbs, cout, cin, kh)
              and (halo_ok or tile_kind(c) != TILE_HALO3X3) and (res_ok or tile_kind(c) != TILE_RESIDENT1X1)]
     cfg = _choose_tile(key, run, cands, variant=None if (halo_ok or res_ok) else "nohalo")
-    return conv2d_q(xq, x_absmax, codes, offset, kh, kw, stride, pad, col_scale, col_shift,
-                    residual=residual, relu=relu, y_absmax=y_absmax, out=out,
-                    tile_cfg=-1 if cfg is None else cfg, emit_range=emit_range, overflow=overflow,
-                    want_f32=want_f32, residual_q=residual_q, residual_range=residual_range)
+    return conv2d_q(*args, tile_cfg=-1 if cfg is None else cfg, **kwargs)
 
 
 def conv2d_nhwc(x, x_absmax, codes, offset, kh, kw, stride, pad, col_scale, col_shift,
@@ -851,10 +821,7 @@ def debug_mfma_i8(a, b):
     _req(a.is_cuda and a.dtype == torch.int8 and a.shape == (16, 64), "debug_mfma: a")
     _req(b.is_cuda and b.dtype == torch.int8 and b.shape == (16, 64), "debug_mfma: b")
     c = torch.empty(16, 16, dtype=torch.int32, device=a.device)
-    lib = _lib.load()
-    with torch.cuda.device(a.device):
-        _lib.check(lib.smpq_debug_mfma_i8(_lib.ptr(a.contiguous()), _lib.ptr(b.contiguous()), _lib.ptr(c),
-                                          _lib.stream_ptr()), "smpq_debug_mfma_i8")
+    _launch(a.device, "smpq_debug_mfma_i8", a.contiguous(), b.contiguous(), c)
     return c
 
 
@@ -871,10 +838,7 @@ def softmax_xent(logits, labels, stats, want_probs=True):
     _req(stats.dtype == torch.float64 and stats.numel() >= 4 and stats.device == logits.device, "softmax_xent: stats")
     probs = torch.empty_like(logits) if want_probs else None
     ws = torch.empty(2 * max(rows, 1), dtype=torch.float32, device=logits.device)
-    with torch.cuda.device(logits.device):
-        _lib.check(_lib.load().smpq_softmax_xent(_lib.ptr(logits), _lib.ptr(labels), rows, cols, _lib.ptr(probs),
-                                                 _lib.ptr(stats), _lib.ptr(ws), _lib.stream_ptr()),
-                   "smpq_softmax_xent")
+    _launch(logits.device, "smpq_softmax_xent", logits, labels, rows, cols, probs, stats, ws)
     return probs
 
 
@@ -888,9 +852,7 @@ def kl_rows(p_ref, p, stats):
     _req(stats.dtype == torch.float64 and stats.numel() >= 2 and stats.device == p.device, "kl_rows: stats")
     rows, cols = p.shape
     ws = torch.empty(max(rows, 1), dtype=torch.float32, device=p.device)
-    with torch.cuda.device(p.device):
-        _lib.check(_lib.load().smpq_kl_rows(_lib.ptr(p_ref), _lib.ptr(p), rows, cols, _lib.ptr(stats), _lib.ptr(ws),
-                                            _lib.stream_ptr()), "smpq_kl_rows")
+    _launch(p.device, "smpq_kl_rows", p_ref, p, rows, cols, stats, ws)
 
 
 def avgpool_fc(x_nhwc, weight, bias, out=None):
@@ -913,10 +875,7 @@ def avgpool_fc(x_nhwc, weight, bias, out=None):
         out = torch.empty(n, nout, dtype=torch.float32, device=x_nhwc.device)
     _req(out.shape == (n, nout) and out.dtype == torch.float32 and out.is_contiguous() and out.device == x_nhwc.device,
          "avgpool_fc: out must be a contiguous [n, nout] fp32 tensor on the input's device")
-    with torch.cuda.device(x_nhwc.device):
-        _lib.check(_lib.load().smpq_avgpool_fc(_lib.ptr(x_nhwc), n, h * w, c, _lib.ptr(wt), _lib.ptr(b), nout,
-                                               _lib.ptr(pooled), _lib.ptr(out), _lib.stream_ptr()),
-                   "smpq_avgpool_fc")
+    _launch(x_nhwc.device, "smpq_avgpool_fc", x_nhwc, n, h * w, c, wt, b, nout, pooled, out)
     return out
 
 
@@ -955,15 +914,7 @@ def bitpack_plan(w2d, qbits, step):
     mode = torch.empty(cout, dtype=torch.int8, device=dev)
     base = torch.empty(4 * cout, dtype=torch.int8, device=dev).view(torch.int32)
     words = torch.empty(4 * cout, dtype=torch.int8, device=dev).view(torch.int32)
-    lib = _lib.load()
-    P = _lib.ptr
-    if w2d.is_cuda:
-        with torch.cuda.device(dev):
-            _lib.check(lib.smpq_bitpack_plan(P(w2d), cout, k, P(qbits), P(step), P(mode), P(base), P(words),
-                                             _lib.stream_ptr()), "smpq_bitpack_plan")
-    else:
-        _lib.check(lib.smpq_bitpack_plan_host(P(w2d), cout, k, P(qbits), P(step), P(mode), P(base), P(words)),
-                   "smpq_bitpack_plan_host")
+    _launch_twin(w2d, "smpq_bitpack_plan", w2d, cout, k, qbits, step, mode, base, words)
     return mode, base, words
 
 
@@ -986,15 +937,7 @@ def bitpack_store(w2d, mode, base, step, word_off, total_words=None):
     _req(cout <= total <= cout * k, "bitpack_store: total_words outside [cout, cout * k]")
     payload = torch.empty(4 * total, dtype=torch.int8, device=dev)
     _req(payload.data_ptr() % 4 == 0, "bitpack_store: payload not word aligned")
-    lib = _lib.load()
-    P = _lib.ptr
-    if w2d.is_cuda:
-        with torch.cuda.device(dev):
-            _lib.check(lib.smpq_bitpack_store(P(w2d), cout, k, P(mode), P(base), P(step), P(word_off), P(payload),
-                                              _lib.stream_ptr()), "smpq_bitpack_store")
-    else:
-        _lib.check(lib.smpq_bitpack_store_host(P(w2d), cout, k, P(mode), P(base), P(step), P(word_off), P(payload)),
-                   "smpq_bitpack_store_host")
+    _launch_twin(w2d, "smpq_bitpack_store", w2d, cout, k, mode, base, step, word_off, payload)
     return payload
 
 
@@ -1015,15 +958,7 @@ def bitpack_load(payload, cout, k, mode, base, step, word_off, out=None):
         out = torch.empty(cout, k, dtype=torch.float32, device=dev)
     _req(out.dtype == torch.float32 and out.numel() == cout * k and out.is_contiguous() and out.device == dev,
          "bitpack_load: out must be a contiguous fp32 tensor of cout * k elements on the payload's device")
-    lib = _lib.load()
-    P = _lib.ptr
-    if payload.is_cuda:
-        with torch.cuda.device(dev):
-            _lib.check(lib.smpq_bitpack_load(P(payload), cout, k, P(mode), P(base), P(step), P(word_off), P(out),
-                                             _lib.stream_ptr()), "smpq_bitpack_load")
-    else:
-        _lib.check(lib.smpq_bitpack_load_host(P(payload), cout, k, P(mode), P(base), P(step), P(word_off), P(out)),
-                   "smpq_bitpack_load_host")
+    _launch_twin(payload, "smpq_bitpack_load", payload, cout, k, mode, base, step, word_off, out)
     return out
 
 
@@ -1085,14 +1020,7 @@ def u8lut_encode(x, lut, out=None):
     _req(torch.is_tensor(out) and out.dtype == torch.uint8 and out.shape == x.shape and out.is_contiguous()
          and out.device == x.device, "u8lut_encode: out must be a contiguous uint8 tensor of x's shape on its device")
     bad = torch.zeros(1, dtype=torch.int32, device=x.device)
-    lib = _lib.load()
-    P = _lib.ptr
-    if x.is_cuda:
-        with torch.cuda.device(x.device):
-            _lib.check(lib.smpq_u8lut_encode(P(x), n, c, hw, P(lut), P(out), P(bad), _lib.stream_ptr()),
-                       "smpq_u8lut_encode")
-    else:
-        _lib.check(lib.smpq_u8lut_encode_host(P(x), n, c, hw, P(lut), P(out), P(bad)), "smpq_u8lut_encode_host")
+    _launch_twin(x, "smpq_u8lut_encode", x, n, c, hw, lut, out, bad)
     return out, bad
 
 
@@ -1107,11 +1035,5 @@ def u8lut_decode(u, lut, out=None):
     _req(torch.is_tensor(out) and out.dtype == torch.float32 and out.shape == u.shape and out.is_contiguous()
          and out.device == u.device and out.data_ptr() % 4 == 0,
          "u8lut_decode: out must be a contiguous fp32 tensor of u's shape on its device")
-    lib = _lib.load()
-    P = _lib.ptr
-    if u.is_cuda:
-        with torch.cuda.device(u.device):
-            _lib.check(lib.smpq_u8lut_decode(P(u), n, c, hw, P(lut), P(out), _lib.stream_ptr()), "smpq_u8lut_decode")
-    else:
-        _lib.check(lib.smpq_u8lut_decode_host(P(u), n, c, hw, P(lut), P(out)), "smpq_u8lut_decode_host")
+    _launch_twin(u, "smpq_u8lut_decode", u, n, c, hw, lut, out)
     return out

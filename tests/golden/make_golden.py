@@ -102,7 +102,7 @@ def reconstruct_r50_mixed():
             if len(members) == counts[col]:
                 cands.append(members)
         assert len(cands) == 1, ("ambiguous/unmatched accepted semilayer", col, len(cands))
-        members = cands[0]
+        (members,) = cands
         param = float(np.sum(ne[members] * ((32 - b) / 32 - (32 - selected[members]) / 32)))
         params += param
         assert abs(params - cum[col]) < 0.5, (col, params, cum[col])

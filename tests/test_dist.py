@@ -167,7 +167,7 @@ def _calib_worker(rank, world, port, q):
             engine._dp_max_(need)
         assert engine.get_dp_group() is None
         engine.set_calibration(net, c)
-        ranges = [net._smpq_ranges[0][k] for k in c.keys]
+        ranges = [engine.model_state(net).ranges.by_conv[k] for k in c.keys]
         q.put((rank, local, ranges, int(need.item())))
     finally:
         dist.destroy_process_group()

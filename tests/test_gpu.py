@@ -984,8 +984,7 @@ def test_graph_replay_matches_eager(gpu):
             assert xcl.data_ptr() == x.data_ptr() and not xcl.is_contiguous()
             g6 = net(xcl)
             engine.GRAPHS_PER_MODEL[0] = 0  # fallback: one graph, inputs copied in
-            net._smpq_graphs = None
-            net._smpq_graph = None
+            engine.model_state(net).graphs.forget()  # every graph; the pool stays
             f1, f2, f3 = net(x2), net(x2.clone()), net(x2.clone())
             engine.USE_GRAPH[0] = False
             e6 = net(xcl.contiguous())
@@ -1298,31 +1297,22 @@ def test_check_stream_fork_capture_replay(gpu, arch, assign):
     net = build_model(gpu, arch, assign)
     x = torch.randn(7, 3, 224, 224, generator=torch.Generator().manual_seed(23)).to(gpu)
     x2 = torch.randn(7, 3, 224, 224, generator=torch.Generator().manual_seed(24)).to(gpu)
-    shipped = engine._capture_locked
+    shipped = engine._capture_body
 
-    def capture_with_check_stream(model, x_in, cal):
-        g = torch.cuda.CUDAGraph()
-        ctx = engine.Ctx(x_in.shape[0], x_in.device, ranges=cal[0], cache=cal[2])
-        pool = getattr(model, "_smpq_pool", None)
-        if pool is None or pool[0] != x_in.device:
-            pool = model._smpq_pool = (x_in.device, torch.cuda.graph_pool_handle())
-        torch.cuda.synchronize()
-        with torch.cuda.graph(g, pool=pool[1], capture_error_mode="thread_local"):
-            ctx.overflow = torch.zeros(2, dtype=torch.int32, device=x_in.device)
-            main = torch.cuda.current_stream()
-            chk = engine._stream((x_in.device, "check"))
-            chk.wait_stream(main)
-            with torch.cuda.stream(chk):
-                cal[3].check(ctx.overflow[1:])
-            y_static = engine._forward(model, x_in, ctx)
-            main.wait_stream(chk)
-        engine.stats["graph_captures"] += 1
-        return g, ctx, y_static
+    def body_with_check_stream(model, x_in, ctx, fp):
+        main = torch.cuda.current_stream()
+        chk = engine._stream((x_in.device, "check"))
+        chk.wait_stream(main)
+        with torch.cuda.stream(chk):
+            fp.check(ctx.overflow[1:])
+        y_static = engine._forward(model, x_in, ctx)
+        main.wait_stream(chk)
+        return y_static
 
     old = engine.CONCURRENT_DS[0], engine.USE_GRAPH[0], engine.STREAMS[0]
     got = []
     try:
-        engine._capture_locked = capture_with_check_stream
+        engine._capture_body = body_with_check_stream
         with torch.no_grad():
             engine.CONCURRENT_DS[0], engine.USE_GRAPH[0], engine.STREAMS[0] = False, False, 1
             net(x)  # calibrate
@@ -1331,7 +1321,7 @@ def test_check_stream_fork_capture_replay(gpu, arch, assign):
                 engine.STREAMS[0], engine.CONCURRENT_DS[0], engine.USE_GRAPH[0] = streams, True, True
                 got += [(net(x), a), (net(x2), a2), (net(x), a), (net(x2), a2)]  # 2 captures, 2 replays
     finally:
-        engine._capture_locked = shipped
+        engine._capture_body = shipped
         engine.CONCURRENT_DS[0], engine.USE_GRAPH[0], engine.STREAMS[0] = old
     torch.cuda.synchronize()
     for i, (g, want) in enumerate(got):

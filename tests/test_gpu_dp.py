@@ -77,16 +77,16 @@ def test_overflow_rerun_only_widens_ranges(gpu):
     x = torch.randn(4, 3, 224, 224, generator=torch.Generator().manual_seed(12)).to(gpu)
     with torch.no_grad():
         net(x)
-        r0 = dict(net._smpq_ranges[0])
+        r0 = dict(engine.model_state(net).ranges.by_conv)
         rep0, o0 = stats["repack"], stats["overflow_reruns"]
         gens = [m._content_gen for m in net.modules() if hasattr(m, "_content_gen")]
         net(torch.cat([x[:3], 6 * x[3:]]))  # one image overflows the calibrated ranges
         assert stats["overflow_reruns"] == o0 + 1
-        r1 = net._smpq_ranges[0]
+        r1 = engine.model_state(net).ranges.by_conv
         assert set(r1) == set(r0) and all(r1[k] >= r0[k] for k in r0)
         assert any(r1[k] > r0[k] for k in r0)
         net(0.5 * x)  # well inside: no further change
-        assert net._smpq_ranges[0] == r1 and stats["overflow_reruns"] == o0 + 1
+        assert engine.model_state(net).ranges.by_conv == r1 and stats["overflow_reruns"] == o0 + 1
     assert stats["repack"] == rep0
     assert [m._content_gen for m in net.modules() if hasattr(m, "_content_gen")] == gens
 

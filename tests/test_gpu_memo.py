@@ -91,14 +91,25 @@ def _snap(rs):
     return [stats[k] for k in COUNTERS] + [rs.report()["resident_passes"], rs.report()["loader_passes"]]
 
 
+def _engine_caches(net):
+    """Identity of everything the engine keeps for ``net``: its state's fields, and the graph
+    cache's per-address entries, fallback entry and pool."""
+    from smpq import engine
+    st = engine.model_state(net)
+    out = {k: id(getattr(st, k)) for k in st.__slots__}
+    out.update({k: id(getattr(st.graphs, k)) for k in ("entries", "fallback", "pool")})
+    out.update({k: id(v) for k, v in net.__dict__.items() if k.startswith("_smpq")})
+    return out
+
+
 def _hit(memo, net, gpu, rs):
     """An evaluation that must be answered from the memo, launching nothing."""
     h, m, before = memo.report()["hits"], memo.report()["misses"], _snap(rs)
-    cached = {k: id(v) for k, v in net.__dict__.items() if k.startswith("_smpq")}
+    cached = _engine_caches(net)
     r = _eval(net, gpu, rs)
     assert memo.report()["hits"] == h + 1 and memo.report()["misses"] == m
     assert _snap(rs) == before
-    assert {k: id(v) for k, v in net.__dict__.items() if k.startswith("_smpq")} == cached  # the engine's caches
+    assert _engine_caches(net) == cached
     return r
 
 

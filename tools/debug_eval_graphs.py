@@ -22,19 +22,18 @@ orig = engine.set_calibration
 
 
 def traced(model, c, widen=True):
-    old = getattr(model, "_smpq_ranges", None)
+    old = engine.model_state(model).ranges
     sig = engine._signature(model)
     if old is not None:
         maxima = c.maxima.cpu().tolist()
         ranges = {k: max(v, 1e-30) * engine.HEADROOM for k, v in zip(c.keys, maxima)}
-        diff = [k for k in ranges if old[0].get(k) != ranges[k]]
-        sdiff = [i for i, (a, b) in enumerate(zip(old[1][2], sig[2])) if a != b] if old[1] != sig else []
+        diff = [k for k in ranges if old.by_conv.get(k) != ranges[k]]
+        sdiff = [i for i, (a, b) in enumerate(zip(old.sig[2], sig[2])) if a != b] if old.sig != sig else []
         print("set_calibration: widen=%s changed=%s sig_equal=%s (differing param/buffer entries %s, convs equal %s) "
-              "ranges_equal=%s (%d differ)" % (widen, c.changed, old[1] == sig, sdiff[:5], old[1][3] == sig[3],
+              "ranges_equal=%s (%d differ)" % (widen, c.changed, old.sig == sig, sdiff[:5], old.sig[3] == sig[3],
                                              not diff, len(diff)), flush=True)
-    before = id(getattr(model, "_smpq_ranges", None))
     orig(model, c, widen)
-    print("  calibration object kept:", before == id(model._smpq_ranges), flush=True)
+    print("  calibration object kept:", old is engine.model_state(model).ranges, flush=True)
 
 
 engine.set_calibration = traced

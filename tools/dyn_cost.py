@@ -41,7 +41,7 @@ with torch.no_grad():
     for _ in range(100):
         engine._signature(net)
     sig_ms = (time.perf_counter() - t0) / 100 * 1e3
-    fp = net._smpq_dyn[1]
+    fp = engine.model_state(net).dyn[1]
     flag = torch.zeros(1, dtype=torch.int32, device=dev)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()

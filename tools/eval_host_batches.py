@@ -63,7 +63,7 @@ def main():
     __graft_entry__.build()
     import functions
     import resnet
-    from smpq import assignments, ops, stats
+    from smpq import assignments, engine, ops, stats
     from smpq.batches import ResidentSet
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
@@ -94,7 +94,7 @@ def main():
                          ("resident_u8", resident)):
         # every loader starts with all of the model's per-address graph slots free, as if it were the
         # only one the process evaluates (the slots are not reclaimed from an earlier loader's inputs)
-        net.__dict__.pop("_smpq_graphs", None)
+        engine.model_state(net).graphs.forget(fallback=False)
         first = functions.evaluate_acc_loss_softmax(net, dev, loader)  # calibration + graph captures (+ the fill)
         if loader is resident:
             # the second evaluation is the first served from the device: it captures the graphs on

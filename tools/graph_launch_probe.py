@@ -43,8 +43,7 @@ def main():
             engine.STREAMS[0] = nst
             for _ in range(3):
                 net(x)  # eager + capture for this layout
-            per = net._smpq_graphs
-            g = [v for k, v in per.items() if k != "base"][0][0]
+            g = next(iter(engine.model_state(net).graphs.entries.values())).graph
             host, step = [], []
             for _ in range(args.reps):
                 torch.cuda.synchronize()

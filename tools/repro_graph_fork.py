@@ -19,7 +19,9 @@ Cases (mode = topology):
                   then slice -> side and side -> slice edges (the round-2 variant)
   torch_prefork_join  the same, each side stream also joined straight into the capture stream
   smpq_check      the real engine with a082ca2's capture (check on its own forked stream), the
-                  test's call sequence (R18 u8, 7 images, STREAMS 1/2/3, CONCURRENT_DS)
+                  test's call sequence (R18 u8, 7 images, STREAMS 1/2/3, CONCURRENT_DS). Only what is
+                  enqueued is a082ca2's (engine._capture_body is swapped): the capture itself is the
+                  engine's, so unlike a082ca2 it runs with capture_error_mode="thread_local"
   smpq_head       the engine as shipped (check on slice 0's stream), the same sequence
   smpq_check50 / smpq_head50  the same with R50 mixed (the test's first parametrization)
 Variants (environment of the child): base; nopc = DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 (the runtime
@@ -132,25 +134,16 @@ def smpq_case(mode):
     from smpq import assignments, engine
     if mode.startswith("smpq_check"):
         # commit a082ca2's capture: the content check on a stream forked only for it
-        def capture_locked(model, x_in, cal):
-            g = torch.cuda.CUDAGraph()
-            ctx = engine.Ctx(x_in.shape[0], x_in.device, ranges=cal[0], cache=cal[2])
-            pool = getattr(model, "_smpq_pool", None)
-            if pool is None or pool[0] != x_in.device:
-                pool = model._smpq_pool = (x_in.device, torch.cuda.graph_pool_handle())
-            torch.cuda.synchronize()
-            with torch.cuda.graph(g, pool=pool[1]):
-                ctx.overflow = torch.zeros(2, dtype=torch.int32, device=x_in.device)
-                main = torch.cuda.current_stream()
-                chk = engine._stream((x_in.device, "check"))
-                chk.wait_stream(main)
-                with torch.cuda.stream(chk):
-                    cal[3].check(ctx.overflow[1:])
-                y_static = engine._forward(model, x_in, ctx)
-                main.wait_stream(chk)
-            engine.stats["graph_captures"] += 1
-            return g, ctx, y_static
-        engine._capture_locked = capture_locked
+        def capture_body(model, x_in, ctx, fp):
+            main = torch.cuda.current_stream()
+            chk = engine._stream((x_in.device, "check"))
+            chk.wait_stream(main)
+            with torch.cuda.stream(chk):
+                fp.check(ctx.overflow[1:])
+            y_static = engine._forward(model, x_in, ctx)
+            main.wait_stream(chk)
+            return y_static
+        engine._capture_body = capture_body
     dev = torch.device("cuda")
     torch.manual_seed(0)
     r50 = mode.endswith("50")
