@@ -496,6 +496,60 @@ int smpq_u8lut_encode(const float* x, int n, int c, int hw, const float* lut, ui
 int smpq_u8lut_decode_host(const uint8_t* u, int n, int c, int hw, const float* lut, float* x);
 int smpq_u8lut_encode_host(const float* x, int n, int c, int hw, const float* lut, uint8_t* u, uint32_t* bad);
 
+/* ---- trial row patch: one output channel of a packed weight operand, in place (normative) -------
+ * A per-channel sensitivity trial (smpq/sensitivity.py) asks what the loss would be with ONE output
+ * channel c of a conv quantized to b bits. With wlimbs >= 2 smpq_pack_weights_ex codes every row
+ * independently of all others (no conv-wide offset, a per-channel shift), so the trial overwrites
+ * that row of the operand with exactly what the normal path (smpq_quantize_channels_ex on the
+ * weight, then smpq_pack_weights_ex with the recorded step, then the BN fold) would have packed,
+ * and puts the saved bytes back afterwards. The fp32 weight is only read.
+ *
+ * Operand (K = kh*kw*cin, cin % 64 == 0, K <= SMPQ_TRIAL_MAX_K):
+ *   codes      int8 [wlimbs][cout][K], k = tap*cin + ci, tap = r*kw + q (smpq_pack_weights_ex)
+ *   codes_km   int8 [wlimbs][K/64][cout][64], the K-major copy (smpq_weights_kmajor), or NULL when
+ *              the caller keeps none; byte (l, c, k) lives at ((l*(K/64) + k/64)*cout + c)*64 + k%64
+ *   wscale     fp32 [cout]; col_scale fp32 [cout] = fl32(wscale * bn_a), bn_a fp32 [cout] the BN
+ *              factor folded onto the weight scale (ones without a BN)
+ * Save area: SMPQ_TRIAL_SAVE_HEADER + wlimbs*K bytes, 4-byte aligned: float[0] = wscale[c],
+ *   float[1] = col_scale[c] (header bytes 8..15 unused), then the row's code bytes, limb-major
+ *   (byte l*K + k). It is written FIRST, on every call that passes validation.
+ * Arithmetic of the new row, per element t of w[c] (IEEE fp32 / double, no contraction):
+ *   1. mn, mx = min / max of the row. mx == mn (a constant channel, where the reference raises
+ *      ZeroDivisionError): status[0] = 1 and no operand byte is written (the save area holds the
+ *      current row, so a restore is harmless).
+ *   2. the quantizer of smpq_quantize_channels_ex: scale = ((double)mx - mn) / (2^b - 1),
+ *      z = rint(mn / scale), s = (float)scale, d = t / s (SMPQ_QSEM_CPU) or t * (float)(1 / scale)
+ *      (SMPQ_QSEM_DEVICE), v = fl32((rintf(d + (float)z) - (float)z) * s).
+ *   3. the coder of smpq_pack_weights_ex for wlimbs >= 2 with step s, WMAX = 32512 (wlimbs 2) or
+ *      8323072 (wlimbs 3): the row is ON THE GRID when s > 0 and every v has m = rintf(v / s) with
+ *      fl32(m * s) == v and |m| <= WMAX. On the grid: sh = the largest shift <= 8*(wlimbs - 1) with
+ *      (max|m| << sh) <= WMAX (0 when max|m| == 0), code = m << sh, wscale = ldexpf(s, -sh).
+ *      Off the grid (fixed point): wscale = max|v| / WMAX (1 when max|v| == 0),
+ *      code = clamp(rint((double)v / wscale), -WMAX, WMAX).
+ *   4. digits: wlimbs balanced base-256 digits, low first: d = ((m + 128) & 255) - 128,
+ *      m = (m - d) >> 8; the last digit is what remains.
+ *   5. wscale[c] and col_scale[c] = fl32(wscale[c] * bn_a[c]) are written last.
+ * One workgroup of 256 threads; plain vector stores; status is int32 [1], caller-zeroed.
+ * smpq_trial_row_restore writes the save area back to both code layouts and the two scalars.
+ * The *_host twins are native C++ with the same arithmetic over the row-major codes (no K-major
+ * copy) for host memory.
+ * Return codes, before any launch or write: SMPQ_E_INVALID for a null pointer (codes_km alone may
+ * be NULL), wlimbs outside 2..3, channel outside [0, cout), semantics not SMPQ_QSEM_*, a
+ * misaligned save area or non-positive sizes; SMPQ_E_SHAPE for cin % 64 != 0 or
+ * K > SMPQ_TRIAL_MAX_K; SMPQ_E_BITS for bits outside 1..16. */
+#define SMPQ_TRIAL_MAX_K 4608
+#define SMPQ_TRIAL_SAVE_HEADER 16
+int smpq_trial_row_patch(const float* w, int cout, int cin, int kh, int kw, int channel, int bits, int semantics,
+                         int wlimbs, const float* bn_a, int8_t* codes, int8_t* codes_km, float* wscale,
+                         float* col_scale, void* save, int32_t* status, smpq_stream_t stream);
+int smpq_trial_row_restore(int cout, int K, int channel, int wlimbs, int8_t* codes, int8_t* codes_km, float* wscale,
+                           float* col_scale, const void* save, smpq_stream_t stream);
+int smpq_trial_row_patch_host(const float* w, int cout, int cin, int kh, int kw, int channel, int bits, int semantics,
+                              int wlimbs, const float* bn_a, int8_t* codes, float* wscale, float* col_scale,
+                              void* save, int32_t* status);
+int smpq_trial_row_restore_host(int cout, int K, int channel, int wlimbs, int8_t* codes, float* wscale,
+                                float* col_scale, const void* save);
+
 /* Diagnostics: one v_mfma_i32_16x16x64_i8 with the kernel's fragment mapping.
  *   a [16][64] int8 row-major, b [16][64] int8 (b[col][k]), c [16][16] int32 row-major */
 int smpq_debug_mfma_i8(const int8_t* a, const int8_t* b, int32_t* c, smpq_stream_t stream);

@@ -23,6 +23,7 @@
 #include <string>
 
 #include "common.h"
+#include "trial_row_host.h"
 
 #pragma clang fp contract(off)
 
@@ -214,6 +215,134 @@ __global__ __launch_bounds__(kQThreads) void pack_weights_ex_kernel(
   }
 }
 
+// Trial row patch (include/smpq.h): channel c of a packed operand (lw >= 2) overwritten with what
+// quantize_channels_kernel at `b` bits followed by pack_weights_ex_kernel with that step would
+// have packed, the fp32 weight only read. The two kernels' arithmetic is restated here (the
+// quantized row lives in LDS instead of the weight), not shared, so their code is untouched.
+// One workgroup. A thread saves and rewrites the same (l, k) bytes and thread 0 the two scalars,
+// so no store of this kernel is ordered against another thread's load.
+__global__ __launch_bounds__(kQThreads) void trial_row_patch_kernel(
+    const float* __restrict__ w, int cout, int cin, int taps, int c, int b, int semantics, int lw,
+    const float* __restrict__ bn_a, int8_t* __restrict__ codes, int8_t* __restrict__ km,
+    float* __restrict__ wscale, float* __restrict__ col_scale, float* __restrict__ save_head,
+    int8_t* __restrict__ save_codes, int32_t* __restrict__ status) {
+  __shared__ float qrow[SMPQ_TRIAL_MAX_K];
+  __shared__ float smem[2 * kQThreads / kWave];
+  __shared__ int ismem[3 * kQThreads / kWave];
+  __shared__ float sabs[kQThreads / kWave];
+  const int K = cin * taps;
+  const size_t wplane = (size_t)cout * K;
+  const float* row = w + (size_t)c * K;
+  for (int k = threadIdx.x; k < K; k += kQThreads)
+    for (int l = 0; l < lw; ++l) save_codes[(size_t)l * K + k] = codes[l * wplane + (size_t)c * K + k];
+  if (threadIdx.x == 0) {
+    save_head[0] = wscale[c];
+    save_head[1] = col_scale[c];
+  }
+  float mn = INFINITY, mx = -INFINITY;
+  for (int i = threadIdx.x; i < K; i += kQThreads) {
+    const float v = row[i];
+    mn = fminf(mn, v);
+    mx = fmaxf(mx, v);
+  }
+  block_minmax(mn, mx, smem);
+  if (mx == mn) {  // constant channel: reported, the operand left as it is
+    if (threadIdx.x == 0) status[0] = 1;
+    return;
+  }
+  // quantize_channels_kernel
+  const double scale = ((double)mx - (double)mn) / (double)((1 << b) - 1);
+  const double zd = rint((double)mn / scale) + 0.0;
+  const float s = (float)scale;
+  const float z32 = (float)zd;
+  const float inv32 = (float)(1.0 / scale);
+  const bool dev = semantics == SMPQ_QSEM_DEVICE;
+  const float wmax = lw >= 3 ? kW24Max : kW16Max;
+  // ... and pack_weights_ex_kernel's on-grid check of the same element, step s
+  int mmin = INT32_MAX, mmax = INT32_MIN, bad = (s > 0.f) ? 0 : 1;
+  float amax = 0.f;
+  for (int i = threadIdx.x; i < K; i += kQThreads) {
+    const float t = row[i];
+    const float d = dev ? __fmul_rn(t, inv32) : __fdiv_rn(t, s);
+    const float q = rintf(d + z32) - z32;
+    const float v = __fmul_rn(q, s);
+    qrow[i] = v;
+    amax = fmaxf(amax, fabsf(v));
+    if (bad) continue;
+    const float mf = rintf(__fdiv_rn(v, s));
+    if (__fmul_rn(mf, s) != v || fabsf(mf) > wmax) {
+      bad = 1;
+      continue;
+    }
+    mmin = min(mmin, (int)mf);
+    mmax = max(mmax, (int)mf);
+  }
+  mmin = wave_min_i(mmin);
+  mmax = wave_max_i(mmax);
+  bad = wave_max_i(bad);
+  amax = wave_max(amax);
+  const int wid = threadIdx.x / kWave, lane = threadIdx.x % kWave;
+  if (lane == 0) {
+    ismem[wid] = mmin;
+    ismem[4 + wid] = mmax;
+    ismem[8 + wid] = bad;
+    sabs[wid] = amax;
+  }
+  __syncthreads();  // (also: qrow is complete)
+  mmin = min(min(ismem[0], ismem[1]), min(ismem[2], ismem[3]));
+  mmax = max(max(ismem[4], ismem[5]), max(ismem[6], ismem[7]));
+  bad = ismem[8] | ismem[9] | ismem[10] | ismem[11];
+  amax = fmaxf(fmaxf(sabs[0], sabs[1]), fmaxf(sabs[2], sabs[3]));
+  const bool fixed = bad != 0;
+  float sc = s;
+  int sh = 0;
+  if (fixed) {
+    sc = amax > 0.f ? amax / wmax : 1.f;
+  } else {
+    const int am = max(abs(mmin), abs(mmax));
+    const int lim = (int)wmax;
+    while (am > 0 && sh < 8 * (lw - 1) && (am << (sh + 1)) <= lim) ++sh;
+    sc = ldexpf(s, -sh);
+  }
+  const int kc = K / 64;
+  for (int k = threadIdx.x; k < K; k += kQThreads) {
+    const int tap = k / cin;
+    const int ci = k - tap * cin;
+    const float v = qrow[ci * taps + tap];
+    int m;
+    if (fixed) m = (int)fmin(fmax(rint((double)v / (double)sc), -(double)wmax), (double)wmax);
+    else m = (int)rintf(__fdiv_rn(v, s)) * (1 << sh);
+    for (int l = 0; l < lw; ++l) {
+      const int lo = (l == lw - 1) ? m : ((m + 128) & 255) - 128;
+      codes[l * wplane + (size_t)c * K + k] = (int8_t)lo;
+      if (km) km[(((size_t)l * kc + (k >> 6)) * cout + c) * 64 + (k & 63)] = (int8_t)lo;
+      m = (m - lo) >> 8;
+    }
+  }
+  if (threadIdx.x == 0) {
+    wscale[c] = sc;
+    col_scale[c] = __fmul_rn(sc, bn_a[c]);
+  }
+}
+
+__global__ __launch_bounds__(kQThreads) void trial_row_restore_kernel(
+    int cout, int K, int c, int lw, int8_t* __restrict__ codes, int8_t* __restrict__ km,
+    float* __restrict__ wscale, float* __restrict__ col_scale, const float* __restrict__ save_head,
+    const int8_t* __restrict__ save_codes) {
+  const size_t wplane = (size_t)cout * K;
+  const int kc = K / 64;
+  for (int k = threadIdx.x; k < K; k += kQThreads)
+    for (int l = 0; l < lw; ++l) {
+      const int8_t v = save_codes[(size_t)l * K + k];
+      codes[l * wplane + (size_t)c * K + k] = v;
+      if (km) km[(((size_t)l * kc + (k >> 6)) * cout + c) * 64 + (k & 63)] = v;
+    }
+  if (threadIdx.x == 0) {
+    wscale[c] = save_head[0];
+    col_scale[c] = save_head[1];
+  }
+}
+
 // ------------------------------------------------------------------------------------------
 // host twin (native C++, same arithmetic)
 // ------------------------------------------------------------------------------------------
@@ -329,4 +458,45 @@ extern "C" int smpq_pack_weights_s2d_ex(const float* w, int cout, int cin, const
 extern "C" int smpq_pack_weights_s2d(const float* w, int cout, int cin, int wlimbs, int8_t* codes, float* wscale,
                                      int32_t* status, smpq_stream_t stream) {
   return smpq_pack_weights_s2d_ex(w, cout, cin, nullptr, wlimbs, codes, wscale, status, stream);
+}
+
+extern "C" int smpq_trial_row_patch(const float* w, int cout, int cin, int kh, int kw, int channel, int bits,
+                                    int semantics, int wlimbs, const float* bn_a, int8_t* codes, int8_t* codes_km,
+                                    float* wscale, float* col_scale, void* save, int32_t* status,
+                                    smpq_stream_t stream) {
+  std::string err;
+  const int rc = trial_row_check(w, cout, cin, kh, kw, channel, bits, semantics, wlimbs, bn_a, codes, wscale,
+                                 col_scale, save, status, &err);
+  if (rc != SMPQ_OK) return fail(rc, err);
+  hipLaunchKernelGGL(trial_row_patch_kernel, dim3(1), dim3(kQThreads), 0, (hipStream_t)stream, w, cout, cin, kh * kw,
+                     channel, bits, semantics, wlimbs, bn_a, codes, codes_km, wscale, col_scale,
+                     static_cast<float*>(save), static_cast<int8_t*>(save) + SMPQ_TRIAL_SAVE_HEADER, status);
+  return check_hip(hipGetLastError(), "trial_row_patch_kernel launch");
+}
+
+extern "C" int smpq_trial_row_restore(int cout, int K, int channel, int wlimbs, int8_t* codes, int8_t* codes_km,
+                                      float* wscale, float* col_scale, const void* save, smpq_stream_t stream) {
+  std::string err;
+  const int rc = trial_restore_check(cout, K, channel, wlimbs, codes, wscale, col_scale, save, &err);
+  if (rc != SMPQ_OK) return fail(rc, err);
+  hipLaunchKernelGGL(trial_row_restore_kernel, dim3(1), dim3(kQThreads), 0, (hipStream_t)stream, cout, K, channel,
+                     wlimbs, codes, codes_km, wscale, col_scale, static_cast<const float*>(save),
+                     static_cast<const int8_t*>(save) + SMPQ_TRIAL_SAVE_HEADER);
+  return check_hip(hipGetLastError(), "trial_row_restore_kernel launch");
+}
+
+extern "C" int smpq_trial_row_patch_host(const float* w, int cout, int cin, int kh, int kw, int channel, int bits,
+                                         int semantics, int wlimbs, const float* bn_a, int8_t* codes, float* wscale,
+                                         float* col_scale, void* save, int32_t* status) {
+  std::string err;
+  const int rc = trial_row_patch_host(w, cout, cin, kh, kw, channel, bits, semantics, wlimbs, bn_a, codes, wscale,
+                                      col_scale, save, status, &err);
+  return rc != SMPQ_OK ? fail(rc, err) : rc;
+}
+
+extern "C" int smpq_trial_row_restore_host(int cout, int K, int channel, int wlimbs, int8_t* codes, float* wscale,
+                                           float* col_scale, const void* save) {
+  std::string err;
+  const int rc = trial_row_restore_host(cout, K, channel, wlimbs, codes, wscale, col_scale, save, &err);
+  return rc != SMPQ_OK ? fail(rc, err) : rc;
 }

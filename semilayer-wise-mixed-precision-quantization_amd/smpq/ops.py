@@ -181,6 +181,68 @@ def weights_kmajor(codes):
     return out
 
 
+# ---- trial row patch (include/smpq.h): one channel of a packed operand, in place ------------------
+TRIAL_MAX_K = 4608
+TRIAL_SAVE_HEADER = 16
+
+
+def trial_save_bytes(wlimbs, K):
+    """Bytes of the save area of one trial row (header + the row's wlimbs * K code bytes)."""
+    return TRIAL_SAVE_HEADER + int(wlimbs) * int(K)
+
+
+def _trial_operand(what, codes, wscale, col_scale, save, channel, km):
+    _req(codes.dtype == torch.int8 and codes.dim() == 3 and codes.is_contiguous() and codes.shape[0] in (2, 3),
+         "%s: codes must be contiguous int8 [LW, cout, K] with LW 2 or 3" % what)
+    lw, cout, K = codes.shape
+    dev = codes.device
+    _req(K % 64 == 0 and K <= TRIAL_MAX_K, "%s: K must be a multiple of 64, at most %d" % (what, TRIAL_MAX_K))
+    _req(0 <= int(channel) < cout, "%s: channel outside [0, cout)" % what)
+    for name, t in (("wscale", wscale), ("col_scale", col_scale)):
+        _req(t.dtype == torch.float32 and t.numel() == cout and t.is_contiguous() and t.device == dev,
+             "%s: %s must be a contiguous fp32 [cout] tensor on the codes' device" % (what, name))
+    _req(save.dtype == torch.int8 and save.dim() == 1 and save.is_contiguous() and save.device == dev
+         and save.numel() >= trial_save_bytes(lw, K) and save.data_ptr() % 4 == 0,
+         "%s: save must be a contiguous, 4-byte aligned int8 tensor of at least trial_save_bytes(LW, K)" % what)
+    if km is not None:
+        _req(dev.type == "cuda" and km.dtype == torch.int8 and km.shape == (lw, K // 64, cout, 64)
+             and km.is_contiguous() and km.device == dev, "%s: K-major codes must be int8 [LW, K/64, cout, 64]" % what)
+    return lw, cout, K
+
+
+def trial_row_patch(w, channel, bits, bn_a, codes, wscale, col_scale, save, status, km=None, semantics=None):
+    """Overwrite row ``channel`` of a packed operand (``codes`` int8 [LW, cout, K] with LW >= 2, its
+    K-major copy ``km`` or None, ``wscale``, ``col_scale`` = wscale * ``bn_a``) with what quantizing
+    that channel of the fp32 weight ``w`` [cout, cin, kh, kw] at ``bits`` and packing it would give;
+    ``w`` is only read. The row's current bytes and scalars go to ``save`` (int8
+    [trial_save_bytes(LW, K)]) first. ``status`` (int32 [1], caller-zeroed) is set to 1 for a
+    constant channel, whose operand stays as it is. Device tensors: one launch on the current
+    stream, no host sync; host tensors: the native twin (no K-major copy)."""
+    _req(w.dtype == torch.float32 and w.dim() == 4 and w.is_contiguous(), "trial_row_patch: need a contiguous fp32 4-D weight")
+    lw, cout, K = _trial_operand("trial_row_patch", codes, wscale, col_scale, save, channel, km)
+    _req(w.device == codes.device and w.shape[0] == cout and w.shape[1] % 64 == 0
+         and w.shape[1] * w.shape[2] * w.shape[3] == K, "trial_row_patch: weight and codes disagree")
+    _req(1 <= int(bits) <= 16, "trial_row_patch: bits outside 1..16")
+    _req(bn_a.dtype == torch.float32 and bn_a.numel() == cout and bn_a.is_contiguous() and bn_a.device == w.device,
+         "trial_row_patch: bn_a must be a contiguous fp32 [cout] tensor on the weight's device")
+    _req(status.dtype == torch.int32 and status.numel() >= 1 and status.device == w.device, "trial_row_patch: status")
+    sem = _qsem(semantics, w.is_cuda)
+    head = (w, cout, int(w.shape[1]), int(w.shape[2]), int(w.shape[3]), int(channel), int(bits), sem, lw, bn_a, codes)
+    if w.is_cuda:
+        _launch(w.device, "smpq_trial_row_patch", *head, km, wscale, col_scale, save, status)
+    else:
+        _launch_twin(w, "smpq_trial_row_patch", *head, wscale, col_scale, save, status)
+
+
+def trial_row_restore(channel, codes, wscale, col_scale, save, km=None):
+    """Put back what trial_row_patch saved: the row's code bytes (both layouts) and its two scalars."""
+    lw, cout, K = _trial_operand("trial_row_restore", codes, wscale, col_scale, save, channel, km)
+    if codes.is_cuda:
+        _launch(codes.device, "smpq_trial_row_restore", cout, K, int(channel), lw, codes, km, wscale, col_scale, save)
+    else:
+        _launch_twin(codes, "smpq_trial_row_restore", cout, K, int(channel), lw, codes, wscale, col_scale, save)
+
+
 def image_quantize_s2d(x, x_absmax, limbs=None):
     """NCHW fp32 images (c <= 4, h, w >= 2) -> space-to-depth limb planes
     [limbs, n, ceil(h/2), ceil(w/2), 16] (channel (dy*2 + dx)*4 + c = pixel (2i+dy, 2j+dx), channel c;

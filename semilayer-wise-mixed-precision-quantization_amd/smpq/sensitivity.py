@@ -1,0 +1,408 @@
+"""Per-channel delta-loss table: what the search drivers read from dataset/resnetNN_deltaloss.csv.
+
+For every output channel of every searched conv and every bit-width, the change of the loss when
+that ONE channel is quantized (its sign decides the channel's semilayer,
+functions.make_divide_minusplusmodels). The reference ships the three files for the torchvision
+weights and no way to make them; ``delta_loss_table`` + ``write_csv`` make one for any model.
+
+A trial never touches a model tensor. The channel's row of the conv's packed operand (codes, their
+K-major copy, wscale, the folded col_scale) is overwritten in place with what the normal path would
+have packed for the quantized channel (ops.trial_row_patch), the captured static-range graphs are
+replayed over every batch, and the saved bytes are put back (ops.trial_row_restore). Signature,
+content fingerprint, installed ranges and graphs stay valid, so a trial costs two small launches
+plus its forwards: no fingerprint, no repack, no calibration, no capture.
+
+What cannot be patched runs through the public API on the model itself ("slow" trials): a conv
+that is not ``patchable``, and a trial whose replay overflowed a static range.
+"""
+import csv
+import math
+import time
+
+import numpy as np
+import torch
+
+from . import assignments, checkpoint, engine, ops
+from .batches import ResidentSet
+from .qconv import QConv2d, stats
+from .quant import channel_wise_quantizationperchan, check_pending
+
+
+def bn_for(net, conv):
+    """The BatchNorm the engine folds onto ``conv`` (convN -> bnN of its block), or None."""
+    for b in assignments.blocks_of(net):
+        for i in (1, 2, 3):
+            if getattr(b, "conv%d" % i, None) is conv:
+                return getattr(b, "bn%d" % i, None)
+    return None
+
+
+def patchable(conv, bn, channel=None):
+    """Can a trial of ``conv`` (folded with ``bn``) patch its packed operand in place? True when
+      * the conv has a ConvPlan whose codes are [LW, cout, K] with LW >= 2 and no offsets (kinds
+        'fixed' and 'exact16': every row coded independently of the others);
+      * another channel stays unquantized whichever channel is tried (``channel``: besides that
+        one), so the normal path would pack the quantized model with the same LW: a trial that
+        completes a conv would turn it 'exact8' there;
+      * the K-major copy on the codes is there exactly when ops.KMAJOR is on;
+      * K is within the patch kernel's row limit."""
+    if not isinstance(conv, QConv2d):
+        return False
+    plan = engine.conv_plan(conv, bn)
+    if plan is None or plan.codes.dim() != 3 or plan.codes.shape[0] < 2 or plan.offset is not None:
+        return False
+    free = conv._bits_host <= 0
+    others = int(free.sum()) - (1 if channel is None or free[int(channel)] else 0)
+    if others < 1:
+        return False
+    if (getattr(plan.codes, "_smpq_km", None) is not None) != bool(ops.KMAJOR[0]):
+        return False
+    return plan.codes.shape[2] % 64 == 0 and plan.codes.shape[2] <= ops.TRIAL_MAX_K
+
+
+def arch_of(net):
+    blocks = assignments.blocks_of(net)
+    if hasattr(blocks[0], "conv3"):
+        return {16: "resnet50"}.get(len(blocks), "resnet-bottleneck-%d" % len(blocks))
+    return {8: "resnet18", 16: "resnet34"}.get(len(blocks), "resnet-basic-%d" % len(blocks))
+
+
+class DeltaLossTable:
+    """One column per (lnum, channel): ``lnum`` and ``cnum`` (0-based) int64 arrays, ``delta[bit]``
+    float64 arrays (trial loss - base loss; nan for a constant channel), ``bits`` in the order of the
+    file's rows (descending). ``base_loss``: the unquantized model's loss through the sweep's own
+    replays (what patched trials are compared with); ``eval_loss``: the same model's loss from an
+    ordinary evaluation (what slow trials are compared with; it equals functions.evaluate_loss)."""
+
+    def __init__(self, arch, lnum, cnum, bits, delta, base_loss, eval_loss=None, report=None):
+        self.arch = arch
+        self.lnum = np.asarray(lnum, dtype=np.int64)
+        self.cnum = np.asarray(cnum, dtype=np.int64)
+        self.bits = tuple(int(b) for b in bits)
+        self.delta = {int(b): np.asarray(delta[b], dtype=np.float64) for b in self.bits}
+        self.base_loss = base_loss
+        self.eval_loss = base_loss if eval_loss is None else eval_loss
+        # per bit [columns, 4]: a patched trial's softmax_xent statistics (loss sum, correct, rows,
+        # batches); nan rows for slow trials and constant channels
+        self.stats = {}
+        self._report = dict(report or {})
+
+    def report(self):
+        """Counters of the sweep: trials, patched, slow by reason, constant channels (listed),
+        and the calibrations, graph captures and repacks seen by the baseline and by the trials."""
+        return dict(self._report)
+
+
+def write_csv(table, path):
+    """The reference's layout (resnet18_main.py:61-84): row 0 lnum, row 1 the 1-based channel, then
+    one row per bit-width, descending; utf-8-sig, repr-exact floats, no empty trailing column."""
+    with open(path, "w", encoding="utf-8-sig", newline="") as f:
+        wr = csv.writer(f)
+        wr.writerow([int(v) for v in table.lnum])
+        wr.writerow([int(v) + 1 for v in table.cnum])
+        for b in table.bits:
+            wr.writerow([repr(float(v)) for v in table.delta[b]])
+
+
+def read_csv(path, bits=None, arch=None):
+    """write_csv's inverse (also reads the reference's files; empty trailing cells are dropped).
+    ``bits``: the bit-width of each value row, default 8, 6, 4(, 2) by the number of rows."""
+    with open(path, encoding="utf-8-sig", newline="") as f:
+        rows = [r for r in csv.reader(f) if r]
+    n = len(rows[0])
+    while n and rows[0][n - 1].strip() == "":
+        n -= 1
+    if bits is None:
+        bits = (8, 6, 4, 2)[:len(rows) - 2]
+    if len(bits) != len(rows) - 2:
+        raise ValueError("smpq: %s has %d value rows, %d bit-widths given" % (path, len(rows) - 2, len(bits)))
+    lnum = [int(v) for v in rows[0][:n]]
+    cnum = [int(v) - 1 for v in rows[1][:n]]
+    delta = {int(b): [float(v) for v in rows[2 + i][:n]] for i, b in enumerate(bits)}
+    return DeltaLossTable(arch, lnum, cnum, bits, delta, None)
+
+
+# ---- the sweep ---------------------------------------------------------------------------------
+class Trial:
+    __slots__ = ("col", "lnum", "conv", "channel", "bit")
+
+    def __init__(self, col, lnum, conv, channel, bit):
+        self.col, self.lnum, self.conv, self.channel, self.bit = col, lnum, conv, channel, bit
+
+
+def _or_flags(dst, ovf):
+    torch.bitwise_or(dst, ovf, out=dst)
+
+
+def run_patched(trials, batches, hooks, table, flags, status):
+    """The patched trials of ONE conv, without a host sync: for trial i patch, forward every batch
+    into ``table[i]`` (float64 [4] softmax_xent statistics), OR the replays' flags into ``flags[i]``
+    (int32 [2]: overflow, stale content), restore. ``status[i]`` is the patch's constant-channel
+    word. ``hooks``: patch(trial, status_word), restore(trial), forward(x) -> (logits, flag tensor),
+    score(logits, y, row), invalidate(trial). The restore runs whatever happens; after an exception
+    the conv's operand is also marked for repacking (invalidate), then the exception goes on."""
+    for i, tr in enumerate(trials):
+        failed = False
+        try:
+            hooks.patch(tr, status[i:i + 1])
+            for x, y in batches:
+                logits, ovf = hooks.forward(x)
+                _or_flags(flags[i], ovf)
+                hooks.score(logits, y, table[i])
+        except BaseException:
+            failed = True
+            raise
+        finally:
+            hooks.restore(tr)
+            if failed:
+                hooks.invalidate(tr)
+
+
+def sweep(groups, batches, hooks, device, out, counts, progress=None):
+    """Every trial of ``groups`` ([(patchable?, [Trial, ...]), ...], one group per conv): the
+    patched ones conv by conv (one host sync per conv), then the slow ones (convs that are not
+    patchable, overflowed trials) through ``hooks.slow(trial) -> loss``. ``out(trial, loss, slow, row)``
+    receives every result (``row``: a patched trial's four statistics, else None); ``counts`` the bookkeeping."""
+    slow = []
+    done = 0
+    for fast, trials in groups:
+        if not fast:
+            slow += [(tr, "not_patchable") for tr in trials]
+            continue
+        table = torch.zeros(len(trials), 4, dtype=torch.float64, device=device)
+        flags = torch.zeros(len(trials), 2, dtype=torch.int32, device=device)
+        status = torch.zeros(len(trials), dtype=torch.int32, device=device)
+        run_patched(trials, batches, hooks, table, flags, status)
+        rows, fl, st = table.tolist(), flags.tolist(), status.tolist()  # the conv's one host sync
+        for tr, row, (ovf, stale), const in zip(trials, rows, fl, st):
+            if stale:
+                raise RuntimeError("smpq: the model's weights changed while the delta-loss sweep ran")
+            if const:
+                counts["constant"].append((tr.lnum, tr.channel, tr.bit))
+                out(tr, math.nan, False, None)
+            elif ovf:
+                counts["overflowed"] += 1
+                slow.append((tr, "overflow"))
+            else:
+                counts["patched"] += 1
+                out(tr, row[0] / row[3], False, row)
+        done += len(trials)
+        if progress is not None:
+            progress(done, counts)
+    for tr, why in slow:
+        counts["slow"][why] = counts["slow"].get(why, 0) + 1
+        try:
+            loss = hooks.slow(tr)
+        except ZeroDivisionError:  # the reference raises on a constant channel (functions.py:40)
+            counts["constant"].append((tr.lnum, tr.channel, tr.bit))
+            loss = math.nan
+        out(tr, loss, True, None)
+        done += 1
+        if progress is not None:
+            progress(done, counts)
+
+
+class _EngineHooks:
+    """The sweep's hooks on the real engine: ``cal`` the StaticRanges installed by the baseline."""
+
+    def __init__(self, net, cal, batches):
+        self.net, self.cal, self.batches = net, cal, batches
+        self._conv = None
+        self._state = None
+
+    def _bind(self, conv):
+        if self._conv is not conv:
+            bn = bn_for(self.net, conv)
+            plan = engine.conv_plan(conv, bn)
+            with torch.no_grad():
+                a = engine._bn_fold(bn)[0].contiguous() if bn is not None else torch.ones_like(plan.col_scale)
+                wscale = conv.packed()[3]
+                lw, _, K = plan.codes.shape
+                self._save = torch.empty(ops.trial_save_bytes(lw, K), dtype=torch.int8, device=plan.codes.device)
+            self._conv, self._plan, self._a, self._wscale = conv, plan, a, wscale
+            self._km = getattr(plan.codes, "_smpq_km", None)
+
+    def patch(self, tr, status):
+        self._bind(tr.conv)
+        ops.trial_row_patch(tr.conv.weight.detach(), tr.channel, tr.bit, self._a, self._plan.codes, self._wscale,
+                            self._plan.col_scale, self._save, status, km=self._km)
+
+    def restore(self, tr):
+        ops.trial_row_restore(tr.channel, self._plan.codes, self._wscale, self._plan.col_scale, self._save, km=self._km)
+
+    def invalidate(self, tr):
+        tr.conv._content_gen += 1
+
+    def forward(self, x):
+        if engine.USE_GRAPH[0]:
+            return engine._graph_forward(self.net, x, self.cal)
+        return engine._static_eager(self.net, x, self.cal)
+
+    def score(self, logits, y, row):
+        ops.softmax_xent(logits.float().contiguous(), y, row, want_probs=False)
+
+    def slow(self, tr):
+        """One trial through the public API on the model itself: quantize the channel, evaluate as
+        functions.evaluate_loss does, put weight and metadata back bitwise."""
+        if self._state is None:
+            self._state = checkpoint.snapshot(self.net)
+        try:
+            channel_wise_quantizationperchan(tr.conv.weight.data, tr.bit, tr.channel)
+            check_pending()
+            return ordinary_loss(self.net, self.batches)
+        finally:
+            try:
+                check_pending()
+            except ZeroDivisionError:
+                pass
+            checkpoint.restore_(self.net, self._state)
+
+
+def ordinary_loss(net, batches):
+    """functions.evaluate_loss on device batches: a fresh calibration on the first batch, the mean
+    over batches of the batch-mean cross entropy from float64 statistics (one host sync)."""
+    acc = None
+    engine.new_evaluation(net)
+    with torch.no_grad():
+        for x, y in batches:
+            out = net(x).float().contiguous()
+            if acc is None:
+                acc = torch.zeros(4, dtype=torch.float64, device=out.device)
+            ops.softmax_xent(out, y, acc, want_probs=False)
+    loss_sum, _, _, count = acc.tolist()
+    return loss_sum / count
+
+
+def _unpatched_pass(hooks, batches, device):
+    """Every batch through the trials' own forward with no patch: (statistics, flags) on the host.
+    (A function of its own: a replay hands out its graph's flag tensor, which lives in the graph
+    pool; nothing here outlives the call, so a later release of the graphs frees the pool whole.)"""
+    base = torch.zeros(4, dtype=torch.float64, device=device)
+    flags = torch.zeros(2, dtype=torch.int32, device=device)
+    with torch.no_grad():
+        for x, y in batches:
+            logits, ovf = hooks.forward(x)
+            _or_flags(flags, ovf)
+            hooks.score(logits, y, base)
+    return base.tolist(), flags.tolist()
+
+
+def _select(net, lnums, channels):
+    convs = assignments.addressable_convs(net)
+    lnums = list(range(1, len(convs) + 1)) if lnums is None else [int(v) for v in lnums]
+    cols = []
+    for ln in lnums:
+        if not 1 <= ln <= len(convs):
+            raise ValueError("smpq: lnum %d outside 1..%d" % (ln, len(convs)))
+        conv = assignments.conv_for_lnum(net, ln)
+        if channels is None:
+            chans = range(conv.out_channels)
+        elif isinstance(channels, dict):
+            chans = channels.get(ln, range(conv.out_channels))
+        else:
+            chans = channels
+        for c in chans:
+            if not 0 <= int(c) < conv.out_channels:
+                raise ValueError("smpq: channel %d outside lnum %d's %d channels" % (c, ln, conv.out_channels))
+            cols.append((ln, conv, int(c)))
+    return cols
+
+
+def delta_loss_table(net, batches, bits=(8, 6, 4), lnums=None, channels=None, progress=None):
+    """The delta-loss table of ``net`` on ``batches`` (a list of (x, y) device tensors, or a
+    ResidentSet): for every selected conv (``lnums``, default all searched convs in
+    assignments.conv_for_lnum's numbering), channel (``channels``: None = all, a sequence for every
+    conv, or {lnum: sequence}) and bit-width, loss(with that one channel quantized) - loss(as it is),
+    the loss being functions.evaluate_loss's: the mean over batches of the batch-mean cross entropy.
+    Static range mode on the GPU without a data-parallel group; ValueError otherwise.
+
+    One ordinary evaluation installs the static ranges (the sweep's only calibration); one pass of
+    the sweep's own replays over the unpatched model captures the graphs and gives ``base_loss``.
+    Patched trials reuse those ranges: their logits differ from a freshly calibrated evaluation of
+    the quantized model below the activation code step. The model, its operands, ranges and graphs
+    are left bitwise as the baseline made them, unless a slow trial ran (those rewrite and restore
+    the model's tensors, after every patched trial is done). ``progress(done, counts)``: called
+    after every conv."""
+    bits = tuple(sorted({int(b) for b in bits}, reverse=True))
+    if not bits or bits[-1] < 1 or bits[0] > 16:
+        raise ValueError("smpq: bit-widths must be within 1..16")
+    if engine.get_range_mode() != "static":
+        raise ValueError("smpq: delta_loss_table needs the static range mode (engine.set_range_mode)")
+    if engine.get_dp_group() is not None:
+        raise ValueError("smpq: delta_loss_table runs on one GPU (no data-parallel group)")
+    p = next(net.parameters())
+    if not p.is_cuda or net.training or not getattr(net, "fused", True):
+        raise ValueError("smpq: delta_loss_table needs an eval-mode smpq ResNet on the GPU")
+    if isinstance(batches, ResidentSet):
+        batches.bind(p.device)
+    else:
+        batches = list(batches)
+        if not batches or any(not (torch.is_tensor(x) and x.device == p.device) for x, _ in batches):
+            raise ValueError("smpq: batches must be (x, y) pairs with x on the model's device, or a ResidentSet")
+        batches = [(x, torch.as_tensor(y).to(p.device)) for x, y in batches]
+    cols = _select(net, lnums, channels)
+
+    before = {k: stats.get(k, 0) for k in ("calibrations", "graph_captures", "repack")}
+    t0 = time.perf_counter()
+    eval_loss = ordinary_loss(net, batches)
+    cal = engine.model_state(net).ranges
+    hooks = _EngineHooks(net, cal, batches)
+    b, bflags = _unpatched_pass(hooks, batches, p.device)  # captures every graph
+    if any(bflags) or engine._signature(net) != cal.sig:
+        raise RuntimeError("smpq: the baseline of the delta-loss sweep did not hold (overflow or changed weights)")
+    base_loss = b[0] / b[3]
+    mid = {k: stats.get(k, 0) for k in before}
+    t1 = time.perf_counter()  # (the pass above ended in a host read)
+
+    groups = []
+    by_conv = {}
+    for col, (ln, conv, c) in enumerate(cols):
+        by_conv.setdefault(ln, (conv, []))[1].append((col, c))
+    with torch.no_grad():
+        const_rows = {}
+        for ln, (conv, chans) in by_conv.items():
+            w2d = conv.weight.detach().reshape(conv.out_channels, -1)
+            const_rows[ln] = (w2d.amax(1) == w2d.amin(1)).tolist()
+    counts = {"patched": 0, "overflowed": 0, "slow": {}, "constant": []}
+    delta = {bit: np.full(len(cols), np.nan, dtype=np.float64) for bit in bits}
+    for ln, (conv, chans) in by_conv.items():
+        bn = bn_for(net, conv)
+        trials = []
+        for col, c in chans:
+            for bit in bits:
+                if const_rows[ln][c]:  # the reference raises there (functions.py:40): nan, listed
+                    counts["constant"].append((ln, c, bit))
+                else:
+                    trials.append(Trial(col, ln, conv, c, bit))
+        ok = {c: patchable(conv, bn, c) for _, c in chans}
+        fast = [tr for tr in trials if ok[tr.channel]]
+        rest = [tr for tr in trials if not ok[tr.channel]]
+        if fast:
+            groups.append((True, fast))
+        if rest:
+            groups.append((False, rest))
+
+    trial_stats = {bit: np.full((len(cols), 4), np.nan, dtype=np.float64) for bit in bits}
+
+    def out(tr, loss, slow, row):
+        delta[tr.bit][tr.col] = loss - (eval_loss if slow else base_loss)
+        if row is not None:
+            trial_stats[tr.bit][tr.col] = row
+
+    with torch.no_grad():
+        sweep(groups, batches, hooks, p.device, out, counts, progress)
+    after = {k: stats.get(k, 0) for k in before}
+    t2 = time.perf_counter()  # (so did the last conv's trials)
+    if not counts["slow"] and (engine._signature(net) != cal.sig or engine.model_state(net).ranges is not cal):
+        raise RuntimeError("smpq: the model changed while the delta-loss sweep ran")
+    report = {"trials": len(cols) * len(bits), "patched": counts["patched"], "overflowed": counts["overflowed"],
+              "slow": dict(counts["slow"]), "constant": list(counts["constant"]),
+              "baseline": {k: mid[k] - before[k] for k in before},
+              "during_trials": {k: after[k] - mid[k] for k in before},
+              "baseline_s": t1 - t0, "trials_s": t2 - t1}
+    for k in before:  # totals seen during the whole call
+        report[{"graph_captures": "captures", "repack": "repacks"}.get(k, k)] = after[k] - before[k]
+    table = DeltaLossTable(arch_of(net), [ln for ln, _, _ in cols], [c for _, _, c in cols], bits, delta, base_loss,
+                           eval_loss, report)
+    table.stats = trial_stats
+    return table
