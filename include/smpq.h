@@ -550,6 +550,42 @@ int smpq_trial_row_patch_host(const float* w, int cout, int cin, int kh, int kw,
 int smpq_trial_row_restore_host(int cout, int K, int channel, int wlimbs, int8_t* codes, float* wscale,
                                 float* col_scale, const void* save);
 
+/* ---- trial rows patch: n output channels of one packed operand at once (normative) --------------
+ * A semilayer trial (smpq/sensitivity.py semilayer_table) quantizes a subset of ONE conv's output
+ * channels. Row i of the call patches channel channels[i] at bits[i] bits exactly as
+ * smpq_trial_row_patch would (steps 1-5 above, the same operand layouts and limits), in one launch
+ * of n workgroups of 256 threads, one per row; plain vector stores.
+ *   channels, bits  int32 [n], device arrays (host arrays for the *_host twins), 1 <= n <= cout
+ *   save            n slots of SMPQ_TRIAL_SAVE_HEADER + wlimbs*K bytes (a multiple of 16, as
+ *                   K % 64 == 0), slot i at save + i * that, each with the single-row layout;
+ *                   4-byte aligned. Every slot is written first, before its row's operand bytes.
+ *   status          int32 [n], caller-zeroed: status[i] = 1 for a constant row, whose operand bytes
+ *                   stay as they are and whose slot holds the current row; the other rows are
+ *                   patched regardless.
+ * The channels must be pairwise distinct: distinct channels own distinct code bytes in both
+ * layouts, distinct scalars and distinct slots, so no workgroup reads what another writes and
+ * nothing is ordered across workgroups. For the device entry points that, each channel's range
+ * and each bit-width are THE CALLER'S DUTY (the lists live in device memory; smpq/ops.py checks
+ * them on the host before the upload). A device entry outside [0, cout) or 1..16 is skipped with
+ * status[i] = 2 instead of written out of bounds; duplicates are undefined. The *_host twins check
+ * all three themselves before any write: SMPQ_E_INVALID for a channel out of range or listed twice,
+ * SMPQ_E_BITS for a bit-width outside 1..16.
+ * smpq_trial_rows_restore writes every slot back (both code layouts and the two scalars).
+ * Return codes, before any launch or write: those of smpq_trial_row_patch, and SMPQ_E_INVALID for
+ * a null channels or bits pointer or n outside 1..cout. */
+int smpq_trial_rows_patch(const float* w, int cout, int cin, int kh, int kw, const int32_t* channels,
+                          const int32_t* bits, int n, int semantics, int wlimbs, const float* bn_a, int8_t* codes,
+                          int8_t* codes_km, float* wscale, float* col_scale, void* save, int32_t* status,
+                          smpq_stream_t stream);
+int smpq_trial_rows_restore(int cout, int K, const int32_t* channels, int n, int wlimbs, int8_t* codes,
+                            int8_t* codes_km, float* wscale, float* col_scale, const void* save,
+                            smpq_stream_t stream);
+int smpq_trial_rows_patch_host(const float* w, int cout, int cin, int kh, int kw, const int32_t* channels,
+                               const int32_t* bits, int n, int semantics, int wlimbs, const float* bn_a, int8_t* codes,
+                               float* wscale, float* col_scale, void* save, int32_t* status);
+int smpq_trial_rows_restore_host(int cout, int K, const int32_t* channels, int n, int wlimbs, int8_t* codes,
+                                 float* wscale, float* col_scale, const void* save);
+
 /* Diagnostics: one v_mfma_i32_16x16x64_i8 with the kernel's fragment mapping.
  *   a [16][64] int8 row-major, b [16][64] int8 (b[col][k]), c [16][16] int32 row-major */
 int smpq_debug_mfma_i8(const int8_t* a, const int8_t* b, int32_t* c, smpq_stream_t stream);

@@ -219,9 +219,11 @@ __global__ __launch_bounds__(kQThreads) void pack_weights_ex_kernel(
 // quantize_channels_kernel at `b` bits followed by pack_weights_ex_kernel with that step would
 // have packed, the fp32 weight only read. The two kernels' arithmetic is restated here (the
 // quantized row lives in LDS instead of the weight), not shared, so their code is untouched.
-// One workgroup. A thread saves and rewrites the same (l, k) bytes and thread 0 the two scalars,
-// so no store of this kernel is ordered against another thread's load.
-__global__ __launch_bounds__(kQThreads) void trial_row_patch_kernel(
+// One workgroup per row. A thread saves and rewrites the same (l, k) bytes and thread 0 the two
+// scalars, so no store is ordered against another thread's load; rows of distinct channels share
+// no byte, so nothing is ordered across workgroups either. The body exists once, for the single-row
+// kernel and the n-row one.
+__device__ __forceinline__ void trial_row_patch_body(
     const float* __restrict__ w, int cout, int cin, int taps, int c, int b, int semantics, int lw,
     const float* __restrict__ bn_a, int8_t* __restrict__ codes, int8_t* __restrict__ km,
     float* __restrict__ wscale, float* __restrict__ col_scale, float* __restrict__ save_head,
@@ -325,7 +327,35 @@ __global__ __launch_bounds__(kQThreads) void trial_row_patch_kernel(
   }
 }
 
-__global__ __launch_bounds__(kQThreads) void trial_row_restore_kernel(
+__global__ __launch_bounds__(kQThreads) void trial_row_patch_kernel(
+    const float* __restrict__ w, int cout, int cin, int taps, int c, int b, int semantics, int lw,
+    const float* __restrict__ bn_a, int8_t* __restrict__ codes, int8_t* __restrict__ km,
+    float* __restrict__ wscale, float* __restrict__ col_scale, float* __restrict__ save_head,
+    int8_t* __restrict__ save_codes, int32_t* __restrict__ status) {
+  trial_row_patch_body(w, cout, cin, taps, c, b, semantics, lw, bn_a, codes, km, wscale, col_scale, save_head,
+                       save_codes, status);
+}
+
+// Workgroup i: row channels[i] at bits[i] bits, save slot i (``slot`` bytes each), status[i]. The
+// lists are the caller's (distinct channels in [0, cout), bits in 1..16); an entry outside those
+// ranges touches nothing and reports 2, so a bad list cannot write out of bounds.
+__global__ __launch_bounds__(kQThreads) void trial_rows_patch_kernel(
+    const float* __restrict__ w, int cout, int cin, int taps, const int32_t* __restrict__ channels,
+    const int32_t* __restrict__ bits, int semantics, int lw, const float* __restrict__ bn_a,
+    int8_t* __restrict__ codes, int8_t* __restrict__ km, float* __restrict__ wscale, float* __restrict__ col_scale,
+    int8_t* __restrict__ save, long long slot, int32_t* __restrict__ status) {
+  const int i = blockIdx.x;
+  const int c = channels[i], b = bits[i];
+  if (c < 0 || c >= cout || b < 1 || b > 16) {
+    if (threadIdx.x == 0) status[i] = 2;
+    return;
+  }
+  int8_t* s = save + (size_t)i * slot;
+  trial_row_patch_body(w, cout, cin, taps, c, b, semantics, lw, bn_a, codes, km, wscale, col_scale,
+                       reinterpret_cast<float*>(s), s + SMPQ_TRIAL_SAVE_HEADER, status + i);
+}
+
+__device__ __forceinline__ void trial_row_restore_body(
     int cout, int K, int c, int lw, int8_t* __restrict__ codes, int8_t* __restrict__ km,
     float* __restrict__ wscale, float* __restrict__ col_scale, const float* __restrict__ save_head,
     const int8_t* __restrict__ save_codes) {
@@ -341,6 +371,24 @@ __global__ __launch_bounds__(kQThreads) void trial_row_restore_kernel(
     wscale[c] = save_head[0];
     col_scale[c] = save_head[1];
   }
+}
+
+__global__ __launch_bounds__(kQThreads) void trial_row_restore_kernel(
+    int cout, int K, int c, int lw, int8_t* __restrict__ codes, int8_t* __restrict__ km,
+    float* __restrict__ wscale, float* __restrict__ col_scale, const float* __restrict__ save_head,
+    const int8_t* __restrict__ save_codes) {
+  trial_row_restore_body(cout, K, c, lw, codes, km, wscale, col_scale, save_head, save_codes);
+}
+
+__global__ __launch_bounds__(kQThreads) void trial_rows_restore_kernel(
+    int cout, int K, const int32_t* __restrict__ channels, int lw, int8_t* __restrict__ codes,
+    int8_t* __restrict__ km, float* __restrict__ wscale, float* __restrict__ col_scale,
+    const int8_t* __restrict__ save, long long slot) {
+  const int c = channels[blockIdx.x];
+  if (c < 0 || c >= cout) return;
+  const int8_t* s = save + (size_t)blockIdx.x * slot;
+  trial_row_restore_body(cout, K, c, lw, codes, km, wscale, col_scale, reinterpret_cast<const float*>(s),
+                         s + SMPQ_TRIAL_SAVE_HEADER);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -498,5 +546,49 @@ extern "C" int smpq_trial_row_restore_host(int cout, int K, int channel, int wli
                                            float* col_scale, const void* save) {
   std::string err;
   const int rc = trial_row_restore_host(cout, K, channel, wlimbs, codes, wscale, col_scale, save, &err);
+  return rc != SMPQ_OK ? fail(rc, err) : rc;
+}
+
+extern "C" int smpq_trial_rows_patch(const float* w, int cout, int cin, int kh, int kw, const int32_t* channels,
+                                     const int32_t* bits, int n, int semantics, int wlimbs, const float* bn_a,
+                                     int8_t* codes, int8_t* codes_km, float* wscale, float* col_scale, void* save,
+                                     int32_t* status, smpq_stream_t stream) {
+  std::string err;
+  const int rc = trial_rows_check(w, cout, cin, kh, kw, channels, bits, n, semantics, wlimbs, bn_a, codes, wscale,
+                                  col_scale, save, status, &err);
+  if (rc != SMPQ_OK) return fail(rc, err);
+  const long long slot = SMPQ_TRIAL_SAVE_HEADER + (long long)wlimbs * cin * kh * kw;
+  hipLaunchKernelGGL(trial_rows_patch_kernel, dim3(n), dim3(kQThreads), 0, (hipStream_t)stream, w, cout, cin, kh * kw,
+                     channels, bits, semantics, wlimbs, bn_a, codes, codes_km, wscale, col_scale,
+                     static_cast<int8_t*>(save), slot, status);
+  return check_hip(hipGetLastError(), "trial_rows_patch_kernel launch");
+}
+
+extern "C" int smpq_trial_rows_restore(int cout, int K, const int32_t* channels, int n, int wlimbs, int8_t* codes,
+                                       int8_t* codes_km, float* wscale, float* col_scale, const void* save,
+                                       smpq_stream_t stream) {
+  std::string err;
+  const int rc = trial_rows_restore_check(cout, K, channels, n, wlimbs, codes, wscale, col_scale, save, &err);
+  if (rc != SMPQ_OK) return fail(rc, err);
+  const long long slot = SMPQ_TRIAL_SAVE_HEADER + (long long)wlimbs * K;
+  hipLaunchKernelGGL(trial_rows_restore_kernel, dim3(n), dim3(kQThreads), 0, (hipStream_t)stream, cout, K, channels,
+                     wlimbs, codes, codes_km, wscale, col_scale, static_cast<const int8_t*>(save), slot);
+  return check_hip(hipGetLastError(), "trial_rows_restore_kernel launch");
+}
+
+extern "C" int smpq_trial_rows_patch_host(const float* w, int cout, int cin, int kh, int kw, const int32_t* channels,
+                                          const int32_t* bits, int n, int semantics, int wlimbs, const float* bn_a,
+                                          int8_t* codes, float* wscale, float* col_scale, void* save,
+                                          int32_t* status) {
+  std::string err;
+  const int rc = trial_rows_patch_host(w, cout, cin, kh, kw, channels, bits, n, semantics, wlimbs, bn_a, codes, wscale,
+                                       col_scale, save, status, &err);
+  return rc != SMPQ_OK ? fail(rc, err) : rc;
+}
+
+extern "C" int smpq_trial_rows_restore_host(int cout, int K, const int32_t* channels, int n, int wlimbs,
+                                            int8_t* codes, float* wscale, float* col_scale, const void* save) {
+  std::string err;
+  const int rc = trial_rows_restore_host(cout, K, channels, n, wlimbs, codes, wscale, col_scale, save, &err);
   return rc != SMPQ_OK ? fail(rc, err) : rc;
 }

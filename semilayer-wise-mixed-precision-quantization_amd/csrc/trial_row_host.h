@@ -1,6 +1,7 @@
 // Host twins of the trial row patch (include/smpq.h, "trial row patch"): native C++, no HIP, so a
 // stand-alone host program (tools/trial_row_sanitize.cpp) can compile them under a sanitizer.
-// quant.hip wraps them as smpq_trial_row_patch_host / smpq_trial_row_restore_host. The arithmetic
+// quant.hip wraps them as smpq_trial_row_patch_host / smpq_trial_row_restore_host and, for n rows of
+// one operand (tools/trial_rows_sanitize.cpp), smpq_trial_rows_patch_host / _restore_host. The arithmetic
 // restates quantize_row_host and pack_weights_ex_kernel (lw >= 2) of quant.hip; FP contraction off.
 #pragma once
 
@@ -19,37 +20,39 @@ namespace smpq {
 // Argument checks shared by the device and host entry points (km may be null); "" when they pass.
 inline int trial_row_check(const void* w, int cout, int cin, int kh, int kw, int channel, int bits, int semantics,
                            int wlimbs, const void* bn_a, const void* codes, const void* wscale,
-                           const void* col_scale, const void* save, const void* status, std::string* err) {
+                           const void* col_scale, const void* save, const void* status, std::string* err,
+                           const char* fn = "smpq_trial_row_patch") {
+  const std::string who(fn);
   if (!w || !bn_a || !codes || !wscale || !col_scale || !save || !status) {
-    *err = "smpq_trial_row_patch: null pointer";
+    *err = who + ": null pointer";
     return SMPQ_E_INVALID;
   }
   if (cout <= 0 || cin <= 0 || kh <= 0 || kw <= 0) {
-    *err = "smpq_trial_row_patch: sizes must be positive";
+    *err = who + ": sizes must be positive";
     return SMPQ_E_INVALID;
   }
   if (wlimbs < 2 || wlimbs > 3) {
-    *err = "smpq_trial_row_patch: wlimbs must be 2 or 3";
+    *err = who + ": wlimbs must be 2 or 3";
     return SMPQ_E_INVALID;
   }
   if (channel < 0 || channel >= cout) {
-    *err = "smpq_trial_row_patch: channel outside [0, cout)";
+    *err = who + ": channel outside [0, cout)";
     return SMPQ_E_INVALID;
   }
   if (semantics != SMPQ_QSEM_CPU && semantics != SMPQ_QSEM_DEVICE) {
-    *err = "smpq_trial_row_patch: semantics must be SMPQ_QSEM_CPU or SMPQ_QSEM_DEVICE";
+    *err = who + ": semantics must be SMPQ_QSEM_CPU or SMPQ_QSEM_DEVICE";
     return SMPQ_E_INVALID;
   }
   if ((uintptr_t)save & 3) {
-    *err = "smpq_trial_row_patch: save area must be 4-byte aligned";
+    *err = who + ": save area must be 4-byte aligned";
     return SMPQ_E_INVALID;
   }
   if (cin % 64 != 0 || (long long)cin * kh * kw > SMPQ_TRIAL_MAX_K) {
-    *err = "smpq_trial_row_patch: cin must be a multiple of 64 and K at most SMPQ_TRIAL_MAX_K";
+    *err = who + ": cin must be a multiple of 64 and K at most SMPQ_TRIAL_MAX_K";
     return SMPQ_E_SHAPE;
   }
   if (bits < 1 || bits > 16) {
-    *err = "smpq_trial_row_patch: bits outside 1..16";
+    *err = who + ": bits outside 1..16";
     return SMPQ_E_BITS;
   }
   return SMPQ_OK;
@@ -72,12 +75,10 @@ inline int trial_restore_check(int cout, int K, int channel, int wlimbs, const v
   return SMPQ_OK;
 }
 
-inline int trial_row_patch_host(const float* w, int cout, int cin, int kh, int kw, int channel, int bits,
-                                int semantics, int wlimbs, const float* bn_a, int8_t* codes, float* wscale,
-                                float* col_scale, void* save, int32_t* status, std::string* err) {
-  const int rc = trial_row_check(w, cout, cin, kh, kw, channel, bits, semantics, wlimbs, bn_a, codes, wscale,
-                                 col_scale, save, status, err);
-  if (rc != SMPQ_OK) return rc;
+// One row, arguments already checked: save, then steps 1-5 of the header.
+inline void trial_row_patch_body_host(const float* w, int cout, int cin, int kh, int kw, int channel, int bits,
+                                      int semantics, int wlimbs, const float* bn_a, int8_t* codes, float* wscale,
+                                      float* col_scale, void* save, int32_t* status) {
   const int taps = kh * kw, K = cin * taps, c = channel;
   const size_t wplane = (size_t)cout * K;
   const float* row = w + (size_t)c * K;
@@ -93,7 +94,7 @@ inline int trial_row_patch_host(const float* w, int cout, int cin, int kh, int k
   }
   if (mx == mn) {
     *status = 1;
-    return SMPQ_OK;
+    return;
   }
   // the quantizer (quantize_row_host), into a scratch row
   const double scale = ((double)mx - (double)mn) / (double)((1 << bits) - 1);
@@ -147,6 +148,16 @@ inline int trial_row_patch_host(const float* w, int cout, int cin, int kh, int k
   }
   wscale[c] = sc;
   col_scale[c] = sc * bn_a[c];
+}
+
+inline int trial_row_patch_host(const float* w, int cout, int cin, int kh, int kw, int channel, int bits,
+                                int semantics, int wlimbs, const float* bn_a, int8_t* codes, float* wscale,
+                                float* col_scale, void* save, int32_t* status, std::string* err) {
+  const int rc = trial_row_check(w, cout, cin, kh, kw, channel, bits, semantics, wlimbs, bn_a, codes, wscale,
+                                 col_scale, save, status, err);
+  if (rc != SMPQ_OK) return rc;
+  trial_row_patch_body_host(w, cout, cin, kh, kw, channel, bits, semantics, wlimbs, bn_a, codes, wscale, col_scale,
+                            save, status);
   return SMPQ_OK;
 }
 
@@ -160,6 +171,95 @@ inline int trial_row_restore_host(int cout, int K, int channel, int wlimbs, int8
   for (int l = 0; l < wlimbs; ++l) std::memcpy(codes + l * wplane + (size_t)channel * K, scodes + (size_t)l * K, K);
   wscale[channel] = shead[0];
   col_scale[channel] = shead[1];
+  return SMPQ_OK;
+}
+
+// ---- n rows of one operand (include/smpq.h, "trial rows patch") ----------------------------------
+// What both rows entry points check without reading the lists (the device one gets device lists).
+inline int trial_rows_check(const void* w, int cout, int cin, int kh, int kw, const void* channels, const void* bits,
+                            int n, int semantics, int wlimbs, const void* bn_a, const void* codes, const void* wscale,
+                            const void* col_scale, const void* save, const void* status, std::string* err) {
+  if (!channels || !bits) {
+    *err = "smpq_trial_rows_patch: null pointer";
+    return SMPQ_E_INVALID;
+  }
+  const int rc = trial_row_check(w, cout, cin, kh, kw, 0, 8, semantics, wlimbs, bn_a, codes, wscale, col_scale, save,
+                                 status, err, "smpq_trial_rows_patch");
+  if (rc != SMPQ_OK) return rc;
+  if (n < 1 || n > cout) {
+    *err = "smpq_trial_rows_patch: n outside 1..cout";
+    return SMPQ_E_INVALID;
+  }
+  return SMPQ_OK;
+}
+
+inline int trial_rows_restore_check(int cout, int K, const void* channels, int n, int wlimbs, const void* codes,
+                                    const void* wscale, const void* col_scale, const void* save, std::string* err) {
+  if (!channels) {
+    *err = "smpq_trial_rows_restore: null pointer";
+    return SMPQ_E_INVALID;
+  }
+  const int rc = trial_restore_check(cout, K, 0, wlimbs, codes, wscale, col_scale, save, err);
+  if (rc != SMPQ_OK) {
+    err->replace(0, std::strlen("smpq_trial_row_restore"), "smpq_trial_rows_restore");
+    return rc;
+  }
+  if (n < 1 || n > cout) {
+    *err = "smpq_trial_rows_restore: n outside 1..cout";
+    return SMPQ_E_INVALID;
+  }
+  return SMPQ_OK;
+}
+
+// The lists themselves (host memory): every channel in range and seen once, every bit-width in 1..16.
+inline int trial_rows_lists_check(const char* fn, int cout, const int32_t* channels, const int32_t* bits, int n,
+                                  std::string* err) {
+  std::vector<char> seen((size_t)cout, 0);
+  for (int i = 0; i < n; ++i) {
+    const int c = channels[i];
+    if (c < 0 || c >= cout) {
+      *err = std::string(fn) + ": channel outside [0, cout)";
+      return SMPQ_E_INVALID;
+    }
+    if (bits && (bits[i] < 1 || bits[i] > 16)) {
+      *err = std::string(fn) + ": bits outside 1..16";
+      return SMPQ_E_BITS;
+    }
+    if (seen[c]) {
+      *err = std::string(fn) + ": channel " + std::to_string(c) + " listed twice";
+      return SMPQ_E_INVALID;
+    }
+    seen[c] = 1;
+  }
+  return SMPQ_OK;
+}
+
+inline int trial_rows_patch_host(const float* w, int cout, int cin, int kh, int kw, const int32_t* channels,
+                                 const int32_t* bits, int n, int semantics, int wlimbs, const float* bn_a,
+                                 int8_t* codes, float* wscale, float* col_scale, void* save, int32_t* status,
+                                 std::string* err) {
+  int rc = trial_rows_check(w, cout, cin, kh, kw, channels, bits, n, semantics, wlimbs, bn_a, codes, wscale, col_scale,
+                            save, status, err);
+  if (rc == SMPQ_OK) rc = trial_rows_lists_check("smpq_trial_rows_patch", cout, channels, bits, n, err);
+  if (rc != SMPQ_OK) return rc;
+  const size_t slot = SMPQ_TRIAL_SAVE_HEADER + (size_t)wlimbs * cin * kh * kw;
+  for (int i = 0; i < n; ++i)
+    trial_row_patch_body_host(w, cout, cin, kh, kw, channels[i], bits[i], semantics, wlimbs, bn_a, codes, wscale,
+                              col_scale, static_cast<int8_t*>(save) + i * slot, status + i);
+  return SMPQ_OK;
+}
+
+inline int trial_rows_restore_host(int cout, int K, const int32_t* channels, int n, int wlimbs, int8_t* codes,
+                                   float* wscale, float* col_scale, const void* save, std::string* err) {
+  int rc = trial_rows_restore_check(cout, K, channels, n, wlimbs, codes, wscale, col_scale, save, err);
+  if (rc == SMPQ_OK) rc = trial_rows_lists_check("smpq_trial_rows_restore", cout, channels, nullptr, n, err);
+  if (rc != SMPQ_OK) return rc;
+  const size_t slot = SMPQ_TRIAL_SAVE_HEADER + (size_t)wlimbs * K;
+  for (int i = 0; i < n; ++i) {
+    rc = trial_row_restore_host(cout, K, channels[i], wlimbs, codes, wscale, col_scale,
+                                static_cast<const int8_t*>(save) + i * slot, err);
+    if (rc != SMPQ_OK) return rc;
+  }
   return SMPQ_OK;
 }
 

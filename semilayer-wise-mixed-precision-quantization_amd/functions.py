@@ -12,15 +12,32 @@ The reference's quirks that change results are kept on purpose (they are what a 
 reproduce): the dummy sentinel rows appended to the caller's lists, the semilayer split on
 ``dlists[i][index] <= 0`` indexed by list position (functions.py:171-173), and the sensitivity
 pass quantizing the caller's net for its first semilayer before switching to fresh models.
+
+SMPQ_PATCHED_SEMILAYERS=1 (read at import, off by default): the sensitivity pass evaluates every
+semilayer after its first as one smpq.sensitivity.semilayer_table on ONE fresh model, patching the
+semilayer's packed weight rows in place instead of quantizing and loading a model per semilayer
+(DESIGN.md 5g). Same lists, indices and print lines; the KL values come from evaluations under the
+fresh model's own static ranges, not from a calibration per semilayer.
 """
+import os
+import sys
+
 import torch
 
-from smpq import engine, memo, ops
+from smpq import engine, memo, ops, sensitivity
 from smpq.batches import DeviceBatches, ResidentSet
 from smpq.models import ResNet
 from smpq.quant import channel_wise_quantizationperchan, quantize_wgt  # noqa: F401
 
 _SENTINEL = [0, 0, 100, 0, 0, 0, 0, 0]
+PATCHED_SEMILAYERS = [os.environ.get("SMPQ_PATCHED_SEMILAYERS", "0") == "1"]
+_PATCHED = {"announced": False, "calls": 0, "semilayers": 0, "fallbacks": 0}
+
+
+def patched_semilayers_report():
+    """Counters of the SMPQ_PATCHED_SEMILAYERS route: calls that took it, semilayers it evaluated
+    through semilayer_table, and calls that fell back to the ordinary route."""
+    return {k: v for k, v in _PATCHED.items() if k != "announced"}
 
 
 def _run_eval(net, device, data_loader, want_probs):
@@ -124,6 +141,105 @@ def _target_conv(layers, arch, layer_index, block_index, lnum):
 
 
 def _make_semilayers(net, device, originaloutputs, listminus, listplus, arch):
+    import imagenet
+    why = _patched_route_refused(imagenet.val_loader) if PATCHED_SEMILAYERS[0] else "off"
+    if PATCHED_SEMILAYERS[0] and not _PATCHED["announced"]:
+        _PATCHED["announced"] = True
+        print("smpq: SMPQ_PATCHED_SEMILAYERS=1 -> the sensitivity pass patches each semilayer's packed weight "
+              "rows on one fresh model (smpq.sensitivity.semilayer_table) instead of quantizing a model per "
+              "semilayer", file=sys.stderr)
+    if why is None:
+        got = _make_semilayers_patched(net, device, originaloutputs, listminus, listplus, arch)
+        if got is not None:
+            return got
+    elif why != "off":
+        _PATCHED["fallbacks"] += 1
+        print("smpq: SMPQ_PATCHED_SEMILAYERS falls back to the ordinary sensitivity pass: %s" % why, file=sys.stderr)
+    return _make_semilayers_ordinary(net, device, originaloutputs, listminus, listplus, arch)
+
+
+def _patched_route_refused(loader):
+    """Why this call cannot take the patched route (None when it can)."""
+    if not (isinstance(loader, ResidentSet) and loader.dev is not None and loader.dev.type == "cuda"):
+        return "imagenet.val_loader is not a ResidentSet bound to a CUDA device"
+    if engine.get_range_mode() != "static":
+        return "the range mode is not static"
+    return None
+
+
+def _walk_semilayers(listminus, listplus):
+    """The reference's walk over the two lists (sentinel rows appended by the caller): the groups of
+    rows that end where the layer number changes, in order."""
+    groups = []
+    for lst in (listminus, listplus):
+        group = []
+        for i, row in enumerate(lst):
+            if row[2] == 100:
+                break
+            group.append(list(row))
+            if row[2] != lst[i + 1][2]:
+                groups.append(group)
+                group = []
+    return groups
+
+
+def _make_semilayers_patched(net, device, originaloutputs, listminus, listplus, arch):
+    """The switch-on route; None (nothing touched yet) when a semilayer cannot be expressed as one
+    semilayer_table trial, so the caller runs the ordinary route."""
+    import imagenet
+    import resnet
+    for lst in (listminus, listplus):
+        lst.append(list(_SENTINEL))
+    groups = _walk_semilayers(listminus, listplus)
+    if any(len({r[3] for r in g}) != len(g) for g in groups[1:]):
+        for lst in (listminus, listplus):  # the ordinary route appends its own
+            lst.pop()
+        _PATCHED["fallbacks"] += 1
+        print("smpq: SMPQ_PATCHED_SEMILAYERS falls back to the ordinary sensitivity pass: a semilayer lists a "
+              "channel twice", file=sys.stderr)
+        return None
+    _PATCHED["calls"] += 1
+    semilayers, orders = [], []
+    if not groups:
+        return semilayers, orders
+
+    def line(group, index, kldiv):
+        print(group[-1][4], 'bit', 'semilayer-No.', index, 'layernumber=', group[-1][2], 'channels=', len(group),
+              'total KL divergence=', kldiv)
+
+    # the first semilayer as ever, on the caller's net (which stays quantized with it)
+    first = groups[0]
+    layers = [net.layer1, net.layer2, net.layer3, net.layer4]
+    param = 0.0
+    for row in first:
+        conv = _target_conv(layers, arch, row[0], row[1], row[2])
+        conv.weight.data = channel_wise_quantizationperchan(conv.weight.data, row[4], row[3])
+        param += conv.weight[row[3]].data.numel() * ((32 - row[4]) / 32)
+    semilayers.append(first)
+    _, _, afteroutputs = evaluate_acc_loss_softmax(net, device, imagenet.val_loader)
+    kldiv = KLdiv(originaloutputs, afteroutputs) / param
+    line(first, 0, kldiv)
+    orders.append([0, kldiv])
+    if len(groups) > 1:
+        fresh = getattr(resnet, arch)(num_classes=1000, pretrained='imagenet')  # ONE model for all the rest
+        fresh.to(device)
+        fresh.eval()
+        table = sensitivity.semilayer_table(
+            fresh, imagenet.val_loader, [(g[0][2], [r[3] for r in g], [r[4] for r in g]) for g in groups[1:]],
+            reference_outputs=originaloutputs)
+        const = table.report()["constant"]
+        if const:  # the reference raises at the first constant channel it quantizes (functions.py:40)
+            raise ZeroDivisionError("float division by zero (constant channel %s of lnum %s)" % (const[0][1], const[0][0]))
+        _PATCHED["semilayers"] += len(groups) - 1
+        for index, group in enumerate(groups[1:], start=1):
+            semilayers.append(group)
+            kldiv = float(table.kl[index - 1]) / float(table.param[index - 1])
+            line(group, index, kldiv)
+            orders.append([index, kldiv])
+    return semilayers, orders
+
+
+def _make_semilayers_ordinary(net, device, originaloutputs, listminus, listplus, arch):
     import imagenet
     import resnet
     semilayers, orders = [], []

@@ -94,6 +94,10 @@ _PROTOS = {
     "smpq_trial_row_restore": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "smpq_trial_row_patch_host": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "smpq_trial_row_restore_host": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "smpq_trial_rows_patch": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "smpq_trial_rows_restore": (_i, [_i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "smpq_trial_rows_patch_host": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "smpq_trial_rows_restore_host": (_i, [_i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "smpq_u8lut_decode": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     "smpq_u8lut_encode": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "smpq_u8lut_decode_host": (_i, [_vp, _i, _i, _i, _vp, _vp]),

@@ -3,6 +3,7 @@
 Every function validates shapes/dtypes/devices on the host before launching, so a kernel
 never sees an operand that disagrees with its grid (no device-side faults on bad input).
 """
+import numbers
 import os
 from collections import namedtuple
 
@@ -191,7 +192,7 @@ def trial_save_bytes(wlimbs, K):
     return TRIAL_SAVE_HEADER + int(wlimbs) * int(K)
 
 
-def _trial_operand(what, codes, wscale, col_scale, save, channel, km):
+def _trial_operand(what, codes, wscale, col_scale, save, channel, km, slots=1):
     _req(codes.dtype == torch.int8 and codes.dim() == 3 and codes.is_contiguous() and codes.shape[0] in (2, 3),
          "%s: codes must be contiguous int8 [LW, cout, K] with LW 2 or 3" % what)
     lw, cout, K = codes.shape
@@ -202,8 +203,9 @@ def _trial_operand(what, codes, wscale, col_scale, save, channel, km):
         _req(t.dtype == torch.float32 and t.numel() == cout and t.is_contiguous() and t.device == dev,
              "%s: %s must be a contiguous fp32 [cout] tensor on the codes' device" % (what, name))
     _req(save.dtype == torch.int8 and save.dim() == 1 and save.is_contiguous() and save.device == dev
-         and save.numel() >= trial_save_bytes(lw, K) and save.data_ptr() % 4 == 0,
-         "%s: save must be a contiguous, 4-byte aligned int8 tensor of at least trial_save_bytes(LW, K)" % what)
+         and save.numel() >= slots * trial_save_bytes(lw, K) and save.data_ptr() % 4 == 0,
+         "%s: save must be a contiguous, 4-byte aligned int8 tensor of at least %strial_save_bytes(LW, K)"
+         % (what, "n * " if slots != 1 else ""))
     if km is not None:
         _req(dev.type == "cuda" and km.dtype == torch.int8 and km.shape == (lw, K // 64, cout, 64)
              and km.is_contiguous() and km.device == dev, "%s: K-major codes must be int8 [LW, K/64, cout, 64]" % what)
@@ -241,6 +243,93 @@ def trial_row_restore(channel, codes, wscale, col_scale, save, km=None):
         _launch(codes.device, "smpq_trial_row_restore", cout, K, int(channel), lw, codes, km, wscale, col_scale, save)
     else:
         _launch_twin(codes, "smpq_trial_row_restore", cout, K, int(channel), lw, codes, wscale, col_scale, save)
+
+
+# ---- trial rows patch (include/smpq.h): n channels of one packed operand, one launch ----------------
+TrialRows = namedtuple("TrialRows", "channels bits n cout")
+
+
+def trial_rows_save_bytes(wlimbs, K, n):
+    """Bytes of the save area of ``n`` trial rows: n slots of trial_save_bytes(wlimbs, K)."""
+    return int(n) * trial_save_bytes(wlimbs, K)
+
+
+def trial_rows_lists(channels, bits, cout, device, what="trial_rows_patch"):
+    """The validated pair of lists of one rows patch on ``device``: TrialRows(channels int32 [n],
+    bits int32 [n], n, cout). ``channels``: a sequence or host tensor, non-empty, each in [0, cout),
+    pairwise distinct; ``bits``: one int for every row or a sequence of the same length, each in
+    1..16. One upload each; a sweep makes the pairs of a conv up front and passes them back in."""
+    ch = torch.as_tensor(channels).reshape(-1)
+    _req(not ch.is_cuda and not ch.is_floating_point() and ch.dtype != torch.bool,
+         "%s: channels must be an integer sequence or host tensor" % what)
+    ch = ch.to(torch.int64)
+    n = ch.numel()
+    _req(n >= 1, "%s: the channel list is empty" % what)
+    _req(n <= int(cout), "%s: more channels than cout" % what)
+    _req(int(ch.min()) >= 0 and int(ch.max()) < int(cout), "%s: channel outside [0, cout)" % what)
+    _req(torch.unique(ch).numel() == n, "%s: a channel is listed twice" % what)
+    if isinstance(bits, numbers.Integral):
+        b = torch.full((n,), int(bits), dtype=torch.int64)
+    else:
+        b = torch.as_tensor(bits).reshape(-1)
+        _req(not b.is_cuda and not b.is_floating_point() and b.dtype != torch.bool,
+             "%s: bits must be an int, an integer sequence or a host tensor" % what)
+        b = b.to(torch.int64)
+        _req(b.numel() == n, "%s: channels and bits differ in length" % what)
+    _req(int(b.min()) >= 1 and int(b.max()) <= 16, "%s: bits outside 1..16" % what)
+    return TrialRows(ch.to(torch.int32).contiguous().to(device), b.to(torch.int32).contiguous().to(device), n, int(cout))
+
+
+def _trial_rows(what, channels, bits, cout, device):
+    if isinstance(channels, TrialRows):
+        _req(channels.cout == cout and channels.channels.device == device,
+             "%s: the uploaded lists belong to another operand" % what)
+        return channels
+    return trial_rows_lists(channels, 8 if bits is None else bits, cout, device, what)  # (a restore reads no bits)
+
+
+def _trial_rows_operand(what, codes, wscale, col_scale, save, channels, bits, km):
+    """_trial_operand's checks for the rows ``channels`` of ``codes``, the save size scaled by n."""
+    _req(torch.is_tensor(codes) and codes.dim() == 3, "%s: codes must be contiguous int8 [LW, cout, K] with LW 2 or 3" % what)
+    rows = _trial_rows(what, channels, bits, codes.shape[1], codes.device)
+    lw, cout, K = _trial_operand(what, codes, wscale, col_scale, save, 0, km, slots=rows.n)
+    return lw, cout, K, rows
+
+
+def trial_rows_patch(w, channels, bits, bn_a, codes, wscale, col_scale, save, status, km=None, semantics=None):
+    """trial_row_patch for the rows ``channels`` (distinct) of one operand in ONE launch, row i at
+    ``bits[i]`` bits (or ``bits`` for all): ``save`` holds trial_rows_save_bytes(LW, K, n) bytes
+    (slot i = row i's single-row save area), ``status`` int32 [n], caller-zeroed (1 = constant
+    channel, left as it is). ``channels`` may be the TrialRows of trial_rows_lists (``bits`` is then
+    ignored). Returns the TrialRows, for the restore."""
+    what = "trial_rows_patch"
+    _req(w.dtype == torch.float32 and w.dim() == 4 and w.is_contiguous(), "%s: need a contiguous fp32 4-D weight" % what)
+    lw, cout, K, rows = _trial_rows_operand(what, codes, wscale, col_scale, save, channels, bits, km)
+    _req(w.device == codes.device and w.shape[0] == cout and w.shape[1] % 64 == 0
+         and w.shape[1] * w.shape[2] * w.shape[3] == K, "%s: weight and codes disagree" % what)
+    _req(bn_a.dtype == torch.float32 and bn_a.numel() == cout and bn_a.is_contiguous() and bn_a.device == w.device,
+         "%s: bn_a must be a contiguous fp32 [cout] tensor on the weight's device" % what)
+    _req(status.dtype == torch.int32 and status.dim() == 1 and status.is_contiguous() and status.numel() >= rows.n
+         and status.device == w.device, "%s: status must be a contiguous int32 [n] tensor on the weight's device" % what)
+    sem = _qsem(semantics, w.is_cuda)
+    head = (w, cout, int(w.shape[1]), int(w.shape[2]), int(w.shape[3]), rows.channels, rows.bits, rows.n, sem, lw,
+            bn_a, codes)
+    if w.is_cuda:
+        _launch(w.device, "smpq_trial_rows_patch", *head, km, wscale, col_scale, save, status)
+    else:
+        _launch_twin(w, "smpq_trial_rows_patch", *head, wscale, col_scale, save, status)
+    return rows
+
+
+def trial_rows_restore(channels, codes, wscale, col_scale, save, km=None):
+    """Put back what trial_rows_patch saved for the same ``channels`` (a sequence or its TrialRows)."""
+    what = "trial_rows_restore"
+    lw, cout, K, rows = _trial_rows_operand(what, codes, wscale, col_scale, save, channels, None, km)
+    if codes.is_cuda:
+        _launch(codes.device, "smpq_trial_rows_restore", cout, K, rows.channels, rows.n, lw, codes, km, wscale,
+                col_scale, save)
+    else:
+        _launch_twin(codes, "smpq_trial_rows_restore", cout, K, rows.channels, rows.n, lw, codes, wscale, col_scale, save)
 
 
 def image_quantize_s2d(x, x_absmax, limbs=None):

@@ -14,6 +14,11 @@ plus its forwards: no fingerprint, no repack, no calibration, no capture (DESIGN
 
 What cannot be patched runs through the public API on the model itself ("slow" trials): a conv
 that is not ``patchable``, and a trial whose replay overflowed a static range.
+
+``semilayer_table`` is the same for the reference's semilayer sensitivity pass
+(functions.make_semilayers_resnetNN): a trial patches ALL rows of one semilayer (a subset of one
+conv's output channels) in one launch (ops.trial_rows_patch), and every batch is scored for loss,
+top-1 and the KL divergence against reference outputs.
 """
 import csv
 import math
@@ -46,18 +51,38 @@ def patchable(conv, bn, channel=None):
         completes a conv would turn it 'exact8' there;
       * the K-major copy on the codes is there exactly when ops.KMAJOR is on;
       * K is within the patch kernel's row limit."""
-    if not isinstance(conv, QConv2d):
+    free = _patchable_operand(conv, bn)
+    if free is None:
         return False
+    others = int(free.sum()) - (1 if channel is None or free[int(channel)] else 0)
+    return others >= 1
+
+
+def _patchable_operand(conv, bn):
+    """patchable's conditions on the operand alone: the conv's free (unquantized) channel mask, or
+    None when its packed operand cannot be patched in place whatever the channels."""
+    if not isinstance(conv, QConv2d):
+        return None
     plan = engine.conv_plan(conv, bn)
     if plan is None or plan.codes.dim() != 3 or plan.codes.shape[0] < 2 or plan.offset is not None:
-        return False
-    free = conv._bits_host <= 0
-    others = int(free.sum()) - (1 if channel is None or free[int(channel)] else 0)
-    if others < 1:
-        return False
+        return None
     if (getattr(plan.codes, "_smpq_km", None) is not None) != bool(ops.KMAJOR[0]):
+        return None
+    if plan.codes.shape[2] % 64 != 0 or plan.codes.shape[2] > ops.TRIAL_MAX_K:
+        return None
+    return np.asarray(conv._bits_host <= 0)
+
+
+def patchable_rows(conv, bn, channels):
+    """patchable for a semilayer trial: patchable's conditions on the operand, and at least one
+    channel OUTSIDE ``channels`` is unquantized (a semilayer that completes a conv would be packed
+    'exact8' on the normal path, with another LW)."""
+    free = _patchable_operand(conv, bn)
+    if free is None:
         return False
-    return plan.codes.shape[2] % 64 == 0 and plan.codes.shape[2] <= ops.TRIAL_MAX_K
+    free = free.copy()
+    free[[int(c) for c in channels]] = False
+    return bool(free.any())
 
 
 def arch_of(net):
@@ -405,4 +430,336 @@ def delta_loss_table(net, batches, bits=(8, 6, 4), lnums=None, channels=None, pr
     table = DeltaLossTable(arch_of(net), [ln for ln, _, _ in cols], [c for _, _, c in cols], bits, delta, base_loss,
                            eval_loss, report)
     table.stats = trial_stats
+    return table
+
+
+# ---- semilayer trials: many rows of one conv per trial -------------------------------
+class Semilayer:
+    """One trial of semilayer_table: ``channels`` (distinct) of conv ``lnum`` at ``bits`` (one
+    bit-width per channel). ``param`` is what functions._make_semilayers accumulates: the sum over
+    the channels of K * (32 - bit) / 32. ``rows``: the hooks' uploaded lists (ops.TrialRows)."""
+    __slots__ = ("index", "lnum", "conv", "channels", "bits", "param", "rows")
+
+    def __init__(self, index, lnum, conv, channels, bits, k_elems):
+        self.index, self.lnum, self.conv = index, lnum, conv
+        self.channels = [int(c) for c in channels]
+        self.bits = [int(b) for b in bits]
+        self.param = 0.0
+        for b in self.bits:  # in the reference's order of accumulation
+            self.param += k_elems * ((32 - b) / 32)
+        self.rows = None
+
+
+class SemilayerTable:
+    """One entry per semilayer, in the order given: ``lnum``, ``channels``, ``bits``, ``param``;
+    ``loss`` (mean over batches of the batch-mean cross entropy), ``acc`` (top-1), ``kl``
+    (functions.KLdiv's sum / images against the reference outputs) as float64 arrays, nan for a
+    semilayer with a constant channel; ``stats`` [., 4] and ``kl_stats`` [., 2] the raw statistics
+    of a patched trial (nan rows for slow ones); ``slow`` marks the trials that ran through the
+    public API. ``base_loss`` / ``eval_loss`` as in DeltaLossTable."""
+
+    def __init__(self, arch, sems, base_loss, eval_loss, report=None):
+        n = len(sems)
+        self.arch = arch
+        self.lnum = np.asarray([s.lnum for s in sems], dtype=np.int64)
+        self.channels = [list(s.channels) for s in sems]
+        self.bits = [list(s.bits) for s in sems]
+        self.param = np.asarray([s.param for s in sems], dtype=np.float64)
+        self.loss = np.full(n, np.nan, dtype=np.float64)
+        self.acc = np.full(n, np.nan, dtype=np.float64)
+        self.kl = np.full(n, np.nan, dtype=np.float64)
+        self.stats = np.full((n, 4), np.nan, dtype=np.float64)
+        self.kl_stats = np.full((n, 2), np.nan, dtype=np.float64)
+        self.slow = np.zeros(n, dtype=bool)
+        self.base_loss, self.eval_loss = base_loss, eval_loss
+        self._report = dict(report or {})
+
+    def report(self):
+        """delta_loss_table's counters, plus ``rows_patched`` (rows over all patched trials) and
+        ``max_rows`` (the largest n of one patch)."""
+        return dict(self._report)
+
+
+def run_patched_rows(sems, batches, refs, hooks, table, kl, flags, status):
+    """The patched semilayer trials of ONE conv, without a host sync; run_patched with n rows per
+    trial. For trial i: patch its rows, forward every batch b and score it against ``refs[b]`` into
+    ``table[i]`` (float64 [4]) and ``kl[i]`` (float64 [2]), OR the replays' flags into ``flags[i]``,
+    restore. ``status[i]`` is the trial's int32 [n] constant-channel words. Hooks: patch(sem, status),
+    restore(sem), forward(x), score_kl(logits, y, ref, row, kl_row), invalidate(sem)."""
+    for i, sem in enumerate(sems):
+        failed = False
+        try:
+            hooks.patch(sem, status[i])
+            for (x, y), ref in zip(batches, refs):
+                logits, ovf = hooks.forward(x)
+                _or_flags(flags[i], ovf)
+                hooks.score_kl(logits, y, ref, table[i], kl[i])
+        except BaseException:
+            failed = True
+            raise
+        finally:
+            hooks.restore(sem)
+            if failed:
+                hooks.invalidate(sem)
+
+
+def sweep_rows(groups, batches, refs, hooks, device, out, counts, progress=None):
+    """sweep for semilayer trials. ``groups``: [(patchable?, [Semilayer, ...]), ...], one group per
+    conv (one host sync per group); ``refs``: the reference softmax per batch. Results go to
+    ``out(sem, loss, acc, kl, slow, row, kl_row)``. A constant channel makes its whole semilayer nan
+    and is listed; an overflowed trial is redone by ``hooks.slow(sem) -> (acc, loss, kl)`` after all
+    patched trials, with the semilayers that are not patchable."""
+    nan = math.nan
+    slow = []
+    done = 0
+    for fast, sems in groups:
+        if not fast:
+            slow += [(sem, "not_patchable") for sem in sems]
+            continue
+        table = torch.zeros(len(sems), 4, dtype=torch.float64, device=device)
+        kl = torch.zeros(len(sems), 2, dtype=torch.float64, device=device)
+        flags = torch.zeros(len(sems), 2, dtype=torch.int32, device=device)
+        words = torch.zeros(sum(len(s.channels) for s in sems), dtype=torch.int32, device=device)
+        status = list(torch.split(words, [len(s.channels) for s in sems]))
+        run_patched_rows(sems, batches, refs, hooks, table, kl, flags, status)
+        rows, kls, fl, st = table.tolist(), kl.tolist(), flags.tolist(), words.tolist()  # the conv's one host sync
+        at = 0
+        for sem, row, klrow, (ovf, stale) in zip(sems, rows, kls, fl):
+            const = [c for c, word in zip(sem.channels, st[at:at + len(sem.channels)]) if word]
+            at += len(sem.channels)
+            if stale:
+                raise RuntimeError("smpq: the model's weights changed while the semilayer sweep ran")
+            if const:
+                counts["constant"] += [(sem.lnum, c, sem.bits[sem.channels.index(c)]) for c in const]
+                out(sem, nan, nan, nan, False, None, None)
+            elif ovf:
+                counts["overflowed"] += 1
+                slow.append((sem, "overflow"))
+            else:
+                counts["patched"] += 1
+                counts["rows_patched"] += len(sem.channels)
+                counts["max_rows"] = max(counts["max_rows"], len(sem.channels))
+                out(sem, row[0] / row[3], row[1] / row[2], klrow[0] / klrow[1], False, row, klrow)
+        done += len(sems)
+        if progress is not None:
+            progress(done, counts)
+    for sem, why in slow:
+        counts["slow"][why] = counts["slow"].get(why, 0) + 1
+        acc, loss, klv = hooks.slow(sem)  # (constant channels never get here: semilayer_table lists them first)
+        out(sem, loss, acc, klv, True, None, None)
+        done += 1
+        if progress is not None:
+            progress(done, counts)
+
+
+class _RowsHooks(_EngineHooks):
+    """sweep_rows's hooks on the real engine. ``reference``: what slow trials are compared with."""
+
+    def __init__(self, net, cal, batches, reference):
+        super().__init__(net, cal, batches)
+        self.reference = reference
+        self._rows_save = None
+
+    def prepare(self, sems):
+        """Upload the lists of every semilayer of one conv up front and size the save area."""
+        conv = sems[0].conv
+        self._bind(conv)
+        lw, cout, K = self._plan.codes.shape
+        for sem in sems:
+            sem.rows = ops.trial_rows_lists(sem.channels, sem.bits, cout, self._plan.codes.device)
+        need = ops.trial_rows_save_bytes(lw, K, max(len(s.channels) for s in sems))
+        if self._rows_save is None or self._rows_save.numel() < need or self._rows_save.device != self._plan.codes.device:
+            self._rows_save = torch.empty(need, dtype=torch.int8, device=self._plan.codes.device)
+
+    def patch(self, sem, status):
+        self._bind(sem.conv)
+        ops.trial_rows_patch(sem.conv.weight.detach(), sem.rows, None, self._a, self._plan.codes, self._wscale,
+                             self._plan.col_scale, self._rows_save, status, km=self._km)
+
+    def restore(self, sem):
+        ops.trial_rows_restore(sem.rows, self._plan.codes, self._wscale, self._plan.col_scale, self._rows_save, km=self._km)
+
+    def invalidate(self, sem):
+        sem.conv._content_gen += 1
+
+    def score_kl(self, logits, y, ref, row, kl_row):
+        probs = ops.softmax_xent(logits.float().contiguous(), y, row, want_probs=True)
+        ops.kl_rows(ref, probs, kl_row)
+
+    def slow(self, sem):
+        """One semilayer through the public API on the model itself: quantize its channels one by
+        one, evaluate as functions.evaluate_acc_loss_softmax does, KL against the reference, put
+        weights and metadata back bitwise. Returns (acc, loss, kl)."""
+        if self._state is None:
+            self._state = checkpoint.snapshot(self.net)
+        try:
+            for c, bit in zip(sem.channels, sem.bits):
+                channel_wise_quantizationperchan(sem.conv.weight.data, bit, c)
+            check_pending()
+            acc, loss, outs = ordinary_eval(self.net, self.batches)
+            return acc, loss, kl_of(self.reference, outs)
+        finally:
+            try:
+                check_pending()
+            except ZeroDivisionError:
+                pass
+            checkpoint.restore_(self.net, self._state)
+
+
+def ordinary_eval(net, batches):
+    """functions.evaluate_acc_loss_softmax on device batches: (top-1 accuracy, mean batch loss, the
+    per-batch softmax outputs), a fresh calibration on the first batch, one host sync."""
+    acc, outs = None, []
+    engine.new_evaluation(net)
+    with torch.no_grad():
+        for x, y in batches:
+            out = net(x).float().contiguous()
+            if acc is None:
+                acc = torch.zeros(4, dtype=torch.float64, device=out.device)
+            outs.append(ops.softmax_xent(out, y, acc, want_probs=True))
+    loss_sum, correct, seen, count = acc.tolist()
+    return correct / seen, loss_sum / count, outs
+
+
+def kl_of(reference, outs):
+    """functions.KLdiv(reference, outs): sum over images of sum_c p * log(p / q), over the images."""
+    st = torch.zeros(2, dtype=torch.float64, device=outs[0].device)
+    for p, q in zip(reference, outs):
+        ops.kl_rows(p.to(q.device), q, st)
+    s, n = st.tolist()
+    return s / n
+
+
+def _unpatched_pass_probs(hooks, batches, device):
+    """_unpatched_pass that also returns each batch's softmax (fresh tensors, outside any graph pool)."""
+    base = torch.zeros(4, dtype=torch.float64, device=device)
+    flags = torch.zeros(2, dtype=torch.int32, device=device)
+    probs = []
+    with torch.no_grad():
+        for x, y in batches:
+            logits, ovf = hooks.forward(x)
+            _or_flags(flags, ovf)
+            probs.append(ops.softmax_xent(logits.float().contiguous(), y, base, want_probs=True))
+    return base.tolist(), flags.tolist(), probs
+
+
+def _semilayers(net, semilayers):
+    convs = assignments.addressable_convs(net)
+    sems = []
+    for index, (ln, channels, bit) in enumerate(semilayers):
+        ln = int(ln)
+        if not 1 <= ln <= len(convs):
+            raise ValueError("smpq: lnum %d outside 1..%d" % (ln, len(convs)))
+        conv = assignments.conv_for_lnum(net, ln)
+        channels = [int(c) for c in channels]
+        bits = [int(bit)] * len(channels) if isinstance(bit, (int, np.integer)) else [int(b) for b in bit]
+        if not channels or len(bits) != len(channels):
+            raise ValueError("smpq: semilayer %d needs channels and one bit-width, or one per channel" % index)
+        if len(set(channels)) != len(channels):
+            raise ValueError("smpq: semilayer %d lists a channel twice" % index)
+        if min(channels) < 0 or max(channels) >= conv.out_channels:
+            raise ValueError("smpq: semilayer %d has a channel outside lnum %d's %d channels" % (index, ln, conv.out_channels))
+        if min(bits) < 1 or max(bits) > 16:
+            raise ValueError("smpq: bit-widths must be within 1..16")
+        sems.append(Semilayer(index, ln, conv, channels, bits, conv.weight[0].numel()))
+    return sems
+
+
+def semilayer_table(net, batches, semilayers, reference_outputs=None, progress=None):
+    """The reference's semilayer sensitivity pass (functions._make_semilayers) on ``net`` as it is:
+    for every ``(lnum, channels, bit)`` of ``semilayers`` (``bit``: one int or one per channel), the
+    loss, top-1 accuracy and KL divergence against ``reference_outputs`` of the model with THOSE
+    channels of that conv quantized, every semilayer starting from the same model. Returns a
+    SemilayerTable. Preconditions and ValueErrors are delta_loss_table's.
+
+    ``reference_outputs``: the per-batch softmax list functions.KLdiv takes; None = the softmax of
+    the unpatched pass (of the ordinary evaluation for slow trials), so no change gives KL exactly 0.
+    A trial patches the semilayer's rows of the conv's packed operand in one launch
+    (ops.trial_rows_patch), replays the captured graphs, scores every batch eagerly and restores;
+    it runs under the baseline's ranges, as delta_loss_table's trials do. Semilayers that are not
+    patchable_rows and overflowed trials run afterwards through the public API on the model itself,
+    which is restored bitwise after each."""
+    if engine.get_range_mode() != "static":
+        raise ValueError("smpq: semilayer_table needs the static range mode (engine.set_range_mode)")
+    if engine.get_dp_group() is not None:
+        raise ValueError("smpq: semilayer_table runs on one GPU (no data-parallel group)")
+    p = next(net.parameters())
+    if not p.is_cuda or net.training or not getattr(net, "fused", True):
+        raise ValueError("smpq: semilayer_table needs an eval-mode smpq ResNet on the GPU")
+    if isinstance(batches, ResidentSet):
+        batches.bind(p.device)
+    else:
+        batches = list(batches)
+        if not batches or any(not (torch.is_tensor(x) and x.device == p.device) for x, _ in batches):
+            raise ValueError("smpq: batches must be (x, y) pairs with x on the model's device, or a ResidentSet")
+        batches = [(x, torch.as_tensor(y).to(p.device)) for x, y in batches]
+    sems = _semilayers(net, semilayers)
+    if reference_outputs is not None:
+        reference_outputs = [r.to(p.device) for r in reference_outputs]
+
+    before = {k: stats.get(k, 0) for k in ("calibrations", "graph_captures", "repack")}
+    t0 = time.perf_counter()
+    _, eval_loss, eval_outs = ordinary_eval(net, batches)
+    cal = engine.model_state(net).ranges
+    hooks = _RowsHooks(net, cal, batches, eval_outs if reference_outputs is None else reference_outputs)
+    b, bflags, base_probs = _unpatched_pass_probs(hooks, batches, p.device)  # captures every graph
+    if any(bflags) or engine._signature(net) != cal.sig:
+        raise RuntimeError("smpq: the baseline of the semilayer sweep did not hold (overflow or changed weights)")
+    base_loss = b[0] / b[3]
+    if reference_outputs is not None and len(reference_outputs) != len(base_probs):  # (a ResidentSet has no len)
+        raise ValueError("smpq: reference_outputs must hold one softmax tensor per batch")
+    refs = base_probs if reference_outputs is None else reference_outputs
+    if reference_outputs is not None:
+        del eval_outs
+    mid = {k: stats.get(k, 0) for k in before}
+    t1 = time.perf_counter()
+
+    counts = {"patched": 0, "overflowed": 0, "slow": {}, "constant": [], "rows_patched": 0, "max_rows": 0}
+    table = SemilayerTable(arch_of(net), sems, base_loss, eval_loss)
+    by_conv = {}
+    for sem in sems:
+        by_conv.setdefault(sem.lnum, []).append(sem)
+    groups = []
+    with torch.no_grad():
+        for ln, group in by_conv.items():
+            conv = group[0].conv
+            bn = bn_for(net, conv)
+            w2d = conv.weight.detach().reshape(conv.out_channels, -1)
+            const_rows = (w2d.amax(1) == w2d.amin(1)).tolist()
+            fast, rest = [], []
+            for sem in group:
+                const = [c for c in sem.channels if const_rows[c]]
+                if const:  # the reference raises there (functions.py:40): the whole semilayer nan, listed
+                    counts["constant"] += [(ln, c, sem.bits[sem.channels.index(c)]) for c in const]
+                elif patchable_rows(conv, bn, sem.channels):
+                    fast.append(sem)
+                else:
+                    rest.append(sem)
+            if fast:
+                hooks.prepare(fast)
+                groups.append((True, fast))
+            if rest:
+                groups.append((False, rest))
+
+    def out(sem, loss, acc, klv, slow, row, kl_row):
+        i = sem.index
+        table.loss[i], table.acc[i], table.kl[i], table.slow[i] = loss, acc, klv, slow
+        if row is not None:
+            table.stats[i], table.kl_stats[i] = row, kl_row
+
+    with torch.no_grad():
+        sweep_rows(groups, batches, refs, hooks, p.device, out, counts, progress)
+    after = {k: stats.get(k, 0) for k in before}
+    t2 = time.perf_counter()
+    if not counts["slow"] and (engine._signature(net) != cal.sig or engine.model_state(net).ranges is not cal):
+        raise RuntimeError("smpq: the model changed while the semilayer sweep ran")
+    report = {"trials": len(sems), "patched": counts["patched"], "overflowed": counts["overflowed"],
+              "slow": dict(counts["slow"]), "constant": list(counts["constant"]),
+              "rows_patched": counts["rows_patched"], "max_rows": counts["max_rows"],
+              "baseline": {k: mid[k] - before[k] for k in before},
+              "during_trials": {k: after[k] - mid[k] for k in before},
+              "baseline_s": t1 - t0, "trials_s": t2 - t1}
+    for k in before:
+        report[{"graph_captures": "captures", "repack": "repacks"}.get(k, k)] = after[k] - before[k]
+    table._report = report
     return table
