@@ -19,6 +19,11 @@ that is not ``patchable``, and a trial whose replay overflowed a static range.
 (functions.make_semilayers_resnetNN): a trial patches ALL rows of one semilayer (a subset of one
 conv's output channels) in one launch (ops.trial_rows_patch), and every batch is scored for loss,
 top-1 and the KL divergence against reference outputs.
+
+With ``suffix=True`` (SMPQ_TRIAL_SUFFIX=1; off by default) both tables visit their convs in block
+order and a trial of a deep enough block forwards only the blocks from that one on, eagerly, from
+block inputs kept by one prefix pass per block (smpq.suffix); the statistics are the
+replayed trial's bit for bit.
 """
 import csv
 import math
@@ -28,6 +33,7 @@ import numpy as np
 import torch
 
 from . import assignments, checkpoint, engine, ops
+from . import suffix as _suffix  # (the tables have a ``suffix`` argument)
 from .batches import ResidentSet
 from .qconv import QConv2d, stats
 from .quant import channel_wise_quantizationperchan, check_pending
@@ -114,7 +120,8 @@ class DeltaLossTable:
 
     def report(self):
         """Counters of the sweep: trials, patched, slow by reason, constant channels (listed),
-        and the calibrations, graph captures and repacks seen by the baseline and by the trials."""
+        and the calibrations, graph captures and repacks seen by the baseline and by the trials;
+        ``suffix``: what the store kept per block (suffix.Plan.report(); {} with the switch off)."""
         return dict(self._report)
 
 
@@ -159,19 +166,26 @@ def _or_flags(dst, ovf):
     torch.bitwise_or(dst, ovf, out=dst)
 
 
-def run_patched(trials, batches, hooks, table, flags, status):
+def _walk(batches, store):
+    """(kept input or None, x, y) per batch: the store's walk, or every batch in full without one."""
+    return ((None, x, y) for x, y in batches) if store is None else store.walk(batches)
+
+
+def run_patched(trials, batches, hooks, table, flags, status, store=None):
     """The patched trials of ONE conv, without a host sync: for trial i patch, forward every batch
     into ``table[i]`` (float64 [4] softmax_xent statistics), OR the replays' flags into ``flags[i]``
     (int32 [2]: overflow, stale content), restore. ``status[i]`` is the patch's constant-channel
     word. ``hooks``: patch(trial, status_word), restore(trial), forward(x) -> (logits, flag tensor),
     score(logits, y, row), invalidate(trial). The restore runs whatever happens; after an exception
-    the conv's operand is also marked for repacking (invalidate), then the exception goes on."""
+    the conv's operand is also marked for repacking (invalidate), then the exception goes on.
+    ``store`` (suffix.Store of the conv's block, or None): a batch it keeps runs through
+    hooks.resume(kept, block) instead, from the kept block input on."""
     for i, tr in enumerate(trials):
         failed = False
         try:
             hooks.patch(tr, status[i:i + 1])
-            for x, y in batches:
-                logits, ovf = hooks.forward(x)
+            for kept, x, y in _walk(batches, store):
+                logits, ovf = hooks.forward(x) if kept is None else hooks.resume(kept, store.block)
                 _or_flags(flags[i], ovf)
                 hooks.score(logits, y, table[i])
         except BaseException:
@@ -183,37 +197,52 @@ def run_patched(trials, batches, hooks, table, flags, status):
                 hooks.invalidate(tr)
 
 
-def sweep(groups, batches, hooks, device, out, counts, progress=None):
+def _by_block(groups, hooks):
+    """``groups`` in block order (stable), so that a table fills the store once per block."""
+    return sorted(groups, key=lambda g: hooks.block_of(g[1][0].conv))
+
+
+def sweep(groups, batches, hooks, device, out, counts, progress=None, plan=None):
     """Every trial of ``groups`` ([(patchable?, [Trial, ...]), ...], one group per conv): the
     patched ones conv by conv (one host sync per conv), then the slow ones (convs that are not
     patchable, overflowed trials) through ``hooks.slow(trial) -> loss``. ``out(trial, loss, slow, row)``
-    receives every result (``row``: a patched trial's four statistics, else None); ``counts`` the bookkeeping."""
+    receives every result (``row``: a patched trial's four statistics, else None); ``counts`` the bookkeeping.
+    ``plan`` (suffix.Plan or None): the groups are visited in block order and the patched trials of
+    a block run from its kept inputs (suffix.enter); the store is released when the block changes,
+    after the last patched trial and on any exception."""
     slow = []
     done = 0
-    for fast, trials in groups:
-        if not fast:
-            slow += [(tr, "not_patchable") for tr in trials]
-            continue
-        table = torch.zeros(len(trials), 4, dtype=torch.float64, device=device)
-        flags = torch.zeros(len(trials), 2, dtype=torch.int32, device=device)
-        status = torch.zeros(len(trials), dtype=torch.int32, device=device)
-        run_patched(trials, batches, hooks, table, flags, status)
-        rows, fl, st = table.tolist(), flags.tolist(), status.tolist()  # the conv's one host sync
-        for tr, row, (ovf, stale), const in zip(trials, rows, fl, st):
-            if stale:
-                raise RuntimeError("smpq: the model's weights changed while the delta-loss sweep ran")
-            if const:
-                counts["constant"].append((tr.lnum, tr.channel, tr.bit))
-                out(tr, math.nan, False, None)
-            elif ovf:
-                counts["overflowed"] += 1
-                slow.append((tr, "overflow"))
-            else:
-                counts["patched"] += 1
-                out(tr, row[0] / row[3], False, row)
-        done += len(trials)
-        if progress is not None:
-            progress(done, counts)
+    if plan is not None:
+        groups = _by_block(groups, hooks)
+    try:
+        for fast, trials in groups:
+            if not fast:
+                slow += [(tr, "not_patchable") for tr in trials]
+                continue
+            store = None if plan is None else _suffix.enter(plan, hooks, trials[0].conv, batches, device)
+            table = torch.zeros(len(trials), 4, dtype=torch.float64, device=device)
+            flags = torch.zeros(len(trials), 2, dtype=torch.int32, device=device)
+            status = torch.zeros(len(trials), dtype=torch.int32, device=device)
+            run_patched(trials, batches, hooks, table, flags, status, store)
+            rows, fl, st = table.tolist(), flags.tolist(), status.tolist()  # the conv's one host sync
+            for tr, row, (ovf, stale), const in zip(trials, rows, fl, st):
+                if stale:
+                    raise RuntimeError("smpq: the model's weights changed while the delta-loss sweep ran")
+                if const:
+                    counts["constant"].append((tr.lnum, tr.channel, tr.bit))
+                    out(tr, math.nan, False, None)
+                elif ovf:
+                    counts["overflowed"] += 1
+                    slow.append((tr, "overflow"))
+                else:
+                    counts["patched"] += 1
+                    out(tr, row[0] / row[3], False, row)
+            done += len(trials)
+            if progress is not None:
+                progress(done, counts)
+    finally:
+        if plan is not None:
+            plan.store.release()
     for tr, why in slow:
         counts["slow"][why] = counts["slow"].get(why, 0) + 1
         try:
@@ -227,8 +256,9 @@ def sweep(groups, batches, hooks, device, out, counts, progress=None):
             progress(done, counts)
 
 
-class _EngineHooks:
-    """The sweep's hooks on the real engine: ``cal`` the StaticRanges installed by the baseline."""
+class _EngineHooks(_suffix.EngineHooks):
+    """The sweep's hooks on the real engine: ``cal`` the StaticRanges installed by the baseline.
+    (suffix.EngineHooks adds what a table with a suffix.Plan calls: block_of, fill, resume.)"""
 
     def __init__(self, net, cal, batches):
         self.net, self.cal, self.batches = net, cal, batches
@@ -249,6 +279,7 @@ class _EngineHooks:
 
     def patch(self, tr, status):
         self._bind(tr.conv)
+        self.new_trial()
         ops.trial_row_patch(tr.conv.weight.detach(), tr.channel, tr.bit, self._a, self._plan.codes, self._wscale,
                             self._plan.col_scale, self._save, status, km=self._km)
 
@@ -333,7 +364,16 @@ def _select(net, lnums, channels):
     return cols
 
 
-def delta_loss_table(net, batches, bits=(8, 6, 4), lnums=None, channels=None, progress=None):
+def _suffix_plan(net, hooks, on, budget, base, base_kl=None):
+    """The table's suffix.Plan (bound to ``hooks``), or None with the switch off."""
+    if not on:
+        return None
+    hooks.plan = _suffix.Plan(budget, base, base_kl, first=_suffix.first_block(net))
+    return hooks.plan
+
+
+def delta_loss_table(net, batches, bits=(8, 6, 4), lnums=None, channels=None, progress=None, suffix=None,
+                     suffix_bytes=None):
     """The delta-loss table of ``net`` on ``batches`` (a list of (x, y) device tensors, or a
     ResidentSet): for every selected conv (``lnums``, default all searched convs in
     assignments.conv_for_lnum's numbering), channel (``channels``: None = all, a sequence for every
@@ -347,7 +387,14 @@ def delta_loss_table(net, batches, bits=(8, 6, 4), lnums=None, channels=None, pr
     the quantized model below the activation code step. The model, its operands, ranges and graphs
     are left bitwise as the baseline made them, unless a slow trial ran (those rewrite and restore
     the model's tensors, after every patched trial is done). ``progress(done, counts)``: called
-    after every conv."""
+    after every conv.
+
+    ``suffix`` (None: SMPQ_TRIAL_SUFFIX, off by default): the convs are visited in block order and
+    the trials of a deep enough block (smpq.suffix.MIN_SKIPPED) forward only the blocks from that one
+    on, eagerly, from block inputs kept by one prefix pass per block under ``suffix_bytes`` (None:
+    SMPQ_TRIAL_SUFFIX_GB, else unbounded); same statistics bit for bit, ``report()["suffix"]`` says
+    what was kept."""
+    use_suffix, budget = _suffix.switch(suffix, suffix_bytes)
     bits = tuple(sorted({int(b) for b in bits}, reverse=True))
     if not bits or bits[-1] < 1 or bits[0] > 16:
         raise ValueError("smpq: bit-widths must be within 1..16")
@@ -376,6 +423,7 @@ def delta_loss_table(net, batches, bits=(8, 6, 4), lnums=None, channels=None, pr
     if any(bflags) or engine._signature(net) != cal.sig:
         raise RuntimeError("smpq: the baseline of the delta-loss sweep did not hold (overflow or changed weights)")
     base_loss = b[0] / b[3]
+    plan = _suffix_plan(net, hooks, use_suffix, budget, b)
     mid = {k: stats.get(k, 0) for k in before}
     t1 = time.perf_counter()  # (the pass above ended in a host read)
 
@@ -415,7 +463,7 @@ def delta_loss_table(net, batches, bits=(8, 6, 4), lnums=None, channels=None, pr
             trial_stats[tr.bit][tr.col] = row
 
     with torch.no_grad():
-        sweep(groups, batches, hooks, p.device, out, counts, progress)
+        sweep(groups, batches, hooks, p.device, out, counts, progress, plan)
     after = {k: stats.get(k, 0) for k in before}
     t2 = time.perf_counter()  # (so did the last conv's trials)
     if not counts["slow"] and (engine._signature(net) != cal.sig or engine.model_state(net).ranges is not cal):
@@ -424,7 +472,7 @@ def delta_loss_table(net, batches, bits=(8, 6, 4), lnums=None, channels=None, pr
               "slow": dict(counts["slow"]), "constant": list(counts["constant"]),
               "baseline": {k: mid[k] - before[k] for k in before},
               "during_trials": {k: after[k] - mid[k] for k in before},
-              "baseline_s": t1 - t0, "trials_s": t2 - t1}
+              "baseline_s": t1 - t0, "trials_s": t2 - t1, "suffix": plan.report() if plan is not None else {}}
     for k in before:  # totals seen during the whole call
         report[{"graph_captures": "captures", "repack": "repacks"}.get(k, k)] = after[k] - before[k]
     table = DeltaLossTable(arch_of(net), [ln for ln, _, _ in cols], [c for _, _, c in cols], bits, delta, base_loss,
@@ -480,18 +528,19 @@ class SemilayerTable:
         return dict(self._report)
 
 
-def run_patched_rows(sems, batches, refs, hooks, table, kl, flags, status):
+def run_patched_rows(sems, batches, refs, hooks, table, kl, flags, status, store=None):
     """The patched semilayer trials of ONE conv, without a host sync; run_patched with n rows per
     trial. For trial i: patch its rows, forward every batch b and score it against ``refs[b]`` into
     ``table[i]`` (float64 [4]) and ``kl[i]`` (float64 [2]), OR the replays' flags into ``flags[i]``,
     restore. ``status[i]`` is the trial's int32 [n] constant-channel words. Hooks: patch(sem, status),
-    restore(sem), forward(x), score_kl(logits, y, ref, row, kl_row), invalidate(sem)."""
+    restore(sem), forward(x), score_kl(logits, y, ref, row, kl_row), invalidate(sem). ``store``: as
+    in run_patched."""
     for i, sem in enumerate(sems):
         failed = False
         try:
             hooks.patch(sem, status[i])
-            for (x, y), ref in zip(batches, refs):
-                logits, ovf = hooks.forward(x)
+            for (kept, x, y), ref in zip(_walk(batches, store), refs):
+                logits, ovf = hooks.forward(x) if kept is None else hooks.resume(kept, store.block)
                 _or_flags(flags[i], ovf)
                 hooks.score_kl(logits, y, ref, table[i], kl[i])
         except BaseException:
@@ -503,46 +552,54 @@ def run_patched_rows(sems, batches, refs, hooks, table, kl, flags, status):
                 hooks.invalidate(sem)
 
 
-def sweep_rows(groups, batches, refs, hooks, device, out, counts, progress=None):
+def sweep_rows(groups, batches, refs, hooks, device, out, counts, progress=None, plan=None):
     """sweep for semilayer trials. ``groups``: [(patchable?, [Semilayer, ...]), ...], one group per
     conv (one host sync per group); ``refs``: the reference softmax per batch. Results go to
     ``out(sem, loss, acc, kl, slow, row, kl_row)``. A constant channel makes its whole semilayer nan
     and is listed; an overflowed trial is redone by ``hooks.slow(sem) -> (acc, loss, kl)`` after all
-    patched trials, with the semilayers that are not patchable."""
+    patched trials, with the semilayers that are not patchable. ``plan``: as in sweep (its
+    self-check also compares the KL statistics)."""
     nan = math.nan
     slow = []
     done = 0
-    for fast, sems in groups:
-        if not fast:
-            slow += [(sem, "not_patchable") for sem in sems]
-            continue
-        table = torch.zeros(len(sems), 4, dtype=torch.float64, device=device)
-        kl = torch.zeros(len(sems), 2, dtype=torch.float64, device=device)
-        flags = torch.zeros(len(sems), 2, dtype=torch.int32, device=device)
-        words = torch.zeros(sum(len(s.channels) for s in sems), dtype=torch.int32, device=device)
-        status = list(torch.split(words, [len(s.channels) for s in sems]))
-        run_patched_rows(sems, batches, refs, hooks, table, kl, flags, status)
-        rows, kls, fl, st = table.tolist(), kl.tolist(), flags.tolist(), words.tolist()  # the conv's one host sync
-        at = 0
-        for sem, row, klrow, (ovf, stale) in zip(sems, rows, kls, fl):
-            const = [c for c, word in zip(sem.channels, st[at:at + len(sem.channels)]) if word]
-            at += len(sem.channels)
-            if stale:
-                raise RuntimeError("smpq: the model's weights changed while the semilayer sweep ran")
-            if const:
-                counts["constant"] += [(sem.lnum, c, sem.bits[sem.channels.index(c)]) for c in const]
-                out(sem, nan, nan, nan, False, None, None)
-            elif ovf:
-                counts["overflowed"] += 1
-                slow.append((sem, "overflow"))
-            else:
-                counts["patched"] += 1
-                counts["rows_patched"] += len(sem.channels)
-                counts["max_rows"] = max(counts["max_rows"], len(sem.channels))
-                out(sem, row[0] / row[3], row[1] / row[2], klrow[0] / klrow[1], False, row, klrow)
-        done += len(sems)
-        if progress is not None:
-            progress(done, counts)
+    if plan is not None:
+        groups = _by_block(groups, hooks)
+    try:
+        for fast, sems in groups:
+            if not fast:
+                slow += [(sem, "not_patchable") for sem in sems]
+                continue
+            store = None if plan is None else _suffix.enter(plan, hooks, sems[0].conv, batches, device, refs)
+            table = torch.zeros(len(sems), 4, dtype=torch.float64, device=device)
+            kl = torch.zeros(len(sems), 2, dtype=torch.float64, device=device)
+            flags = torch.zeros(len(sems), 2, dtype=torch.int32, device=device)
+            words = torch.zeros(sum(len(s.channels) for s in sems), dtype=torch.int32, device=device)
+            status = list(torch.split(words, [len(s.channels) for s in sems]))
+            run_patched_rows(sems, batches, refs, hooks, table, kl, flags, status, store)
+            rows, kls, fl, st = table.tolist(), kl.tolist(), flags.tolist(), words.tolist()  # the conv's one host sync
+            at = 0
+            for sem, row, klrow, (ovf, stale) in zip(sems, rows, kls, fl):
+                const = [c for c, word in zip(sem.channels, st[at:at + len(sem.channels)]) if word]
+                at += len(sem.channels)
+                if stale:
+                    raise RuntimeError("smpq: the model's weights changed while the semilayer sweep ran")
+                if const:
+                    counts["constant"] += [(sem.lnum, c, sem.bits[sem.channels.index(c)]) for c in const]
+                    out(sem, nan, nan, nan, False, None, None)
+                elif ovf:
+                    counts["overflowed"] += 1
+                    slow.append((sem, "overflow"))
+                else:
+                    counts["patched"] += 1
+                    counts["rows_patched"] += len(sem.channels)
+                    counts["max_rows"] = max(counts["max_rows"], len(sem.channels))
+                    out(sem, row[0] / row[3], row[1] / row[2], klrow[0] / klrow[1], False, row, klrow)
+            done += len(sems)
+            if progress is not None:
+                progress(done, counts)
+    finally:
+        if plan is not None:
+            plan.store.release()
     for sem, why in slow:
         counts["slow"][why] = counts["slow"].get(why, 0) + 1
         acc, loss, klv = hooks.slow(sem)  # (constant channels never get here: semilayer_table lists them first)
@@ -573,6 +630,7 @@ class _RowsHooks(_EngineHooks):
 
     def patch(self, sem, status):
         self._bind(sem.conv)
+        self.new_trial()
         ops.trial_rows_patch(sem.conv.weight.detach(), sem.rows, None, self._a, self._plan.codes, self._wscale,
                              self._plan.col_scale, self._rows_save, status, km=self._km)
 
@@ -665,7 +723,7 @@ def _semilayers(net, semilayers):
     return sems
 
 
-def semilayer_table(net, batches, semilayers, reference_outputs=None, progress=None):
+def semilayer_table(net, batches, semilayers, reference_outputs=None, progress=None, suffix=None, suffix_bytes=None):
     """The reference's semilayer sensitivity pass (functions._make_semilayers) on ``net`` as it is:
     for every ``(lnum, channels, bit)`` of ``semilayers`` (``bit``: one int or one per channel), the
     loss, top-1 accuracy and KL divergence against ``reference_outputs`` of the model with THOSE
@@ -678,7 +736,8 @@ def semilayer_table(net, batches, semilayers, reference_outputs=None, progress=N
     (ops.trial_rows_patch), replays the captured graphs, scores every batch eagerly and restores;
     it runs under the baseline's ranges, as delta_loss_table's trials do. Semilayers that are not
     patchable_rows and overflowed trials run afterwards through the public API on the model itself,
-    which is restored bitwise after each."""
+    which is restored bitwise after each. ``suffix`` / ``suffix_bytes``: as in delta_loss_table."""
+    use_suffix, budget = _suffix.switch(suffix, suffix_bytes)
     if engine.get_range_mode() != "static":
         raise ValueError("smpq: semilayer_table needs the static range mode (engine.set_range_mode)")
     if engine.get_dp_group() is not None:
@@ -711,6 +770,12 @@ def semilayer_table(net, batches, semilayers, reference_outputs=None, progress=N
     refs = base_probs if reference_outputs is None else reference_outputs
     if reference_outputs is not None:
         del eval_outs
+    plan = None
+    if use_suffix:  # what a block's self-check must reproduce: the unpatched pass's KL statistics too
+        base_kl = torch.zeros(2, dtype=torch.float64, device=p.device)
+        for ref, probs in zip(refs, base_probs):
+            ops.kl_rows(ref, probs, base_kl)
+        plan = _suffix_plan(net, hooks, True, budget, b, base_kl.tolist())
     mid = {k: stats.get(k, 0) for k in before}
     t1 = time.perf_counter()
 
@@ -748,7 +813,7 @@ def semilayer_table(net, batches, semilayers, reference_outputs=None, progress=N
             table.stats[i], table.kl_stats[i] = row, kl_row
 
     with torch.no_grad():
-        sweep_rows(groups, batches, refs, hooks, p.device, out, counts, progress)
+        sweep_rows(groups, batches, refs, hooks, p.device, out, counts, progress, plan)
     after = {k: stats.get(k, 0) for k in before}
     t2 = time.perf_counter()
     if not counts["slow"] and (engine._signature(net) != cal.sig or engine.model_state(net).ranges is not cal):
@@ -758,7 +823,7 @@ def semilayer_table(net, batches, semilayers, reference_outputs=None, progress=N
               "rows_patched": counts["rows_patched"], "max_rows": counts["max_rows"],
               "baseline": {k: mid[k] - before[k] for k in before},
               "during_trials": {k: after[k] - mid[k] for k in before},
-              "baseline_s": t1 - t0, "trials_s": t2 - t1}
+              "baseline_s": t1 - t0, "trials_s": t2 - t1, "suffix": plan.report() if plan is not None else {}}
     for k in before:
         report[{"graph_captures": "captures", "repack": "repacks"}.get(k, k)] = after[k] - before[k]
     table._report = report
