@@ -586,6 +586,62 @@ int smpq_trial_rows_patch_host(const float* w, int cout, int cin, int kh, int kw
 int smpq_trial_rows_restore_host(int cout, int K, const int32_t* channels, int n, int wlimbs, int8_t* codes,
                                  float* wscale, float* col_scale, const void* save);
 
+/* ---- trial rows patch, exact8 operands: rows of a fully quantized conv's operand (normative) -----
+ * A conv whose every channel is quantized is packed by smpq_pack_weights_ex with wlimbs == 1: one
+ * int8 plane, a per-channel offset that the conv kernels read from memory at run time, wscale = the
+ * recorded step. That coder too reads nothing but the row itself (its codes, offset[c], wscale[c]),
+ * so a search trial that RE-quantizes some channels of such a conv (smpq/search.py) overwrites
+ * their rows in place, as smpq_trial_rows_patch does for wlimbs >= 2, with exactly what
+ * smpq_quantize_channels_ex on the weight, smpq_pack_weights_ex(wlimbs = 1) with the new steps and
+ * the BN fold would have left there. The fp32 weight is only read.
+ *
+ * Operand (K = kh*kw*cin, cin % 64 == 0, K <= SMPQ_TRIAL_MAX_K):
+ *   codes      int8 [1][cout][K], k = tap*cin + ci; codes_km int8 [1][K/64][cout][64] or NULL
+ *   offset     int32 [cout], or NULL for an operand packed without offsets (the conv kernels then
+ *              run without them, so a row that needs one cannot be patched: status 4)
+ *   wscale, col_scale, bn_a   as for smpq_trial_row_patch
+ *   channels, bits, status    int32 [n] as for smpq_trial_rows_patch, bits within 1..8
+ *   save       n slots of SMPQ_TRIAL_SAVE_HEADER + K bytes, 4-byte aligned, slot i at save + i * that:
+ *              float[0] = wscale[c], float[1] = col_scale[c], the int32 at byte 8 = offset[c] (0 when
+ *              offset == NULL), bytes 12..15 unused, then the row's K code bytes. A slot is written
+ *              FIRST, before its row's operand bytes.
+ * Arithmetic of row c at b bits (IEEE fp32 / double, no contraction):
+ *   1-2. steps 1 and 2 of smpq_trial_row_patch: the row's min / max, the constant row (status 1),
+ *      the quantizer under both semantics, giving s and the quantized values v.
+ *   3. the wlimbs == 1 coder of smpq_pack_weights_ex with step s: the row is ON THE GRID when s > 0
+ *      and every v has m = rintf(v / s) with fl32(m * s) == v and |m| <= 32512. mmin / mmax = the
+ *      smallest / largest m. Off the grid, or mmax - mmin > 255: status 3 (the normal path would
+ *      not pack this conv exact8).
+ *   4. o = mmin + 128 when mmin < -128 or mmax > 127, else 0. o != 0 with offset == NULL: status 4.
+ *   5. code = m - o, one int8, to both layouts; then offset[c] = o (when offset != NULL),
+ *      wscale[c] = s, col_scale[c] = fl32(s * bn_a[c]).
+ * status[i] (caller-zeroed): 0 patched; 1 constant row; 2 list entry out of range (a channel
+ * outside [0, cout): nothing touched; a bit-width outside 1..8, since a wider row cannot be exact8:
+ * the slot is written); 3; 4. On every nonzero status the row's operand bytes stay as they are, and
+ * except for a channel out of range its slot holds the current row, so a restore is harmless.
+ * One workgroup of 256 threads per row; plain vector stores; distinct channels own distinct bytes,
+ * scalars and slots, so nothing is ordered across workgroups. Lists as for smpq_trial_rows_patch:
+ * the device entry points leave range and distinctness to the caller (smpq/ops.py checks them
+ * before the upload); the *_host twins check them first (SMPQ_E_INVALID; SMPQ_E_BITS for a
+ * bit-width outside 1..8).
+ * smpq_trial_rows_restore_x8 writes every slot back: both code layouts, offset[c] when
+ * offset != NULL, the two scalars.
+ * Return codes, before any launch or write: SMPQ_E_INVALID for a null pointer (codes_km and offset
+ * may be NULL), non-positive sizes, n outside 1..cout, semantics not SMPQ_QSEM_*, a misaligned save
+ * area; SMPQ_E_SHAPE for cin % 64 != 0 (restore: K % 64 != 0) or K > SMPQ_TRIAL_MAX_K. */
+int smpq_trial_rows_patch_x8(const float* w, int cout, int cin, int kh, int kw, const int32_t* channels,
+                             const int32_t* bits, int n, int semantics, const float* bn_a, int8_t* codes,
+                             int8_t* codes_km, int32_t* offset, float* wscale, float* col_scale, void* save,
+                             int32_t* status, smpq_stream_t stream);
+int smpq_trial_rows_restore_x8(int cout, int K, const int32_t* channels, int n, int8_t* codes, int8_t* codes_km,
+                               int32_t* offset, float* wscale, float* col_scale, const void* save,
+                               smpq_stream_t stream);
+int smpq_trial_rows_patch_x8_host(const float* w, int cout, int cin, int kh, int kw, const int32_t* channels,
+                                  const int32_t* bits, int n, int semantics, const float* bn_a, int8_t* codes,
+                                  int32_t* offset, float* wscale, float* col_scale, void* save, int32_t* status);
+int smpq_trial_rows_restore_x8_host(int cout, int K, const int32_t* channels, int n, int8_t* codes, int32_t* offset,
+                                    float* wscale, float* col_scale, const void* save);
+
 /* Diagnostics: one v_mfma_i32_16x16x64_i8 with the kernel's fragment mapping.
  *   a [16][64] int8 row-major, b [16][64] int8 (b[col][k]), c [16][16] int32 row-major */
 int smpq_debug_mfma_i8(const int8_t* a, const int8_t* b, int32_t* c, smpq_stream_t stream);

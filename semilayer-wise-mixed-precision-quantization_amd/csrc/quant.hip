@@ -391,6 +391,128 @@ __global__ __launch_bounds__(kQThreads) void trial_rows_restore_kernel(
                          s + SMPQ_TRIAL_SAVE_HEADER);
 }
 
+// Trial rows patch for an 'exact8' operand (include/smpq.h): one int8 plane, a per-channel offset
+// read by the conv kernels at run time, wscale = the step. quantize_channels_kernel and the lw == 1
+// branch of pack_weights_ex_kernel restated with step s, as above. Workgroup i: row channels[i] at
+// bits[i] bits (1..8), slot i, status[i]; a row that the normal path would not pack exact8 (3) or
+// that needs an offset the operand does not have (4) is reported and left as it is. A thread
+// saves and rewrites the same k bytes and thread 0 the three scalars.
+__global__ __launch_bounds__(kQThreads) void trial_rows_patch_x8_kernel(
+    const float* __restrict__ w, int cout, int cin, int taps, const int32_t* __restrict__ channels,
+    const int32_t* __restrict__ bits, int semantics, const float* __restrict__ bn_a, int8_t* __restrict__ codes,
+    int8_t* __restrict__ km, int32_t* __restrict__ offset, float* __restrict__ wscale, float* __restrict__ col_scale,
+    int8_t* __restrict__ save, long long slot, int32_t* __restrict__ status) {
+  __shared__ float qrow[SMPQ_TRIAL_MAX_K];
+  __shared__ float smem[2 * kQThreads / kWave];
+  __shared__ int ismem[3 * kQThreads / kWave];
+  const int i = blockIdx.x;
+  const int c = channels[i], b = bits[i];
+  if (c < 0 || c >= cout) {  // nothing of this entry can be addressed
+    if (threadIdx.x == 0) status[i] = 2;
+    return;
+  }
+  const int K = cin * taps;
+  const float* row = w + (size_t)c * K;
+  int8_t* crow = codes + (size_t)c * K;
+  int8_t* sv = save + (size_t)i * slot;
+  for (int k = threadIdx.x; k < K; k += kQThreads) sv[SMPQ_TRIAL_SAVE_HEADER + k] = crow[k];
+  if (threadIdx.x == 0) {
+    reinterpret_cast<float*>(sv)[0] = wscale[c];
+    reinterpret_cast<float*>(sv)[1] = col_scale[c];
+    reinterpret_cast<int32_t*>(sv)[2] = offset ? offset[c] : 0;
+  }
+  if (b < 1 || b > 8) {  // a wider row cannot be exact8
+    if (threadIdx.x == 0) status[i] = 2;
+    return;
+  }
+  float mn = INFINITY, mx = -INFINITY;
+  for (int k = threadIdx.x; k < K; k += kQThreads) {
+    const float v = row[k];
+    mn = fminf(mn, v);
+    mx = fmaxf(mx, v);
+  }
+  block_minmax(mn, mx, smem);
+  if (mx == mn) {  // constant channel
+    if (threadIdx.x == 0) status[i] = 1;
+    return;
+  }
+  const double scale = ((double)mx - (double)mn) / (double)((1 << b) - 1);
+  const double zd = rint((double)mn / scale) + 0.0;
+  const float s = (float)scale;
+  const float z32 = (float)zd;
+  const float inv32 = (float)(1.0 / scale);
+  const bool dev = semantics == SMPQ_QSEM_DEVICE;
+  int mmin = INT32_MAX, mmax = INT32_MIN, bad = (s > 0.f) ? 0 : 1;
+  for (int k = threadIdx.x; k < K; k += kQThreads) {
+    const float t = row[k];
+    const float d = dev ? __fmul_rn(t, inv32) : __fdiv_rn(t, s);
+    const float q = rintf(d + z32) - z32;
+    const float v = __fmul_rn(q, s);
+    qrow[k] = v;
+    if (bad) continue;
+    const float mf = rintf(__fdiv_rn(v, s));
+    if (__fmul_rn(mf, s) != v || fabsf(mf) > kW16Max) {
+      bad = 1;
+      continue;
+    }
+    mmin = min(mmin, (int)mf);
+    mmax = max(mmax, (int)mf);
+  }
+  mmin = wave_min_i(mmin);
+  mmax = wave_max_i(mmax);
+  bad = wave_max_i(bad);
+  const int wid = threadIdx.x / kWave, lane = threadIdx.x % kWave;
+  if (lane == 0) {
+    ismem[wid] = mmin;
+    ismem[4 + wid] = mmax;
+    ismem[8 + wid] = bad;
+  }
+  __syncthreads();  // (also: qrow is complete)
+  mmin = min(min(ismem[0], ismem[1]), min(ismem[2], ismem[3]));
+  mmax = max(max(ismem[4], ismem[5]), max(ismem[6], ismem[7]));
+  bad = ismem[8] | ismem[9] | ismem[10] | ismem[11];
+  if (bad || mmax - mmin > 255) {  // the normal path would not pack this conv exact8
+    if (threadIdx.x == 0) status[i] = 3;
+    return;
+  }
+  const int o = (mmin < -128 || mmax > 127) ? mmin + 128 : 0;
+  if (o != 0 && !offset) {
+    if (threadIdx.x == 0) status[i] = 4;
+    return;
+  }
+  for (int k = threadIdx.x; k < K; k += kQThreads) {
+    const int tap = k / cin;
+    const int ci = k - tap * cin;
+    const int8_t code = (int8_t)((int)rintf(__fdiv_rn(qrow[ci * taps + tap], s)) - o);
+    crow[k] = code;
+    if (km) km[((size_t)(k >> 6) * cout + c) * 64 + (k & 63)] = code;
+  }
+  if (threadIdx.x == 0) {
+    if (offset) offset[c] = o;
+    wscale[c] = s;
+    col_scale[c] = __fmul_rn(s, bn_a[c]);
+  }
+}
+
+__global__ __launch_bounds__(kQThreads) void trial_rows_restore_x8_kernel(
+    int cout, int K, const int32_t* __restrict__ channels, int8_t* __restrict__ codes, int8_t* __restrict__ km,
+    int32_t* __restrict__ offset, float* __restrict__ wscale, float* __restrict__ col_scale,
+    const int8_t* __restrict__ save, long long slot) {
+  const int c = channels[blockIdx.x];
+  if (c < 0 || c >= cout) return;
+  const int8_t* sv = save + (size_t)blockIdx.x * slot;
+  for (int k = threadIdx.x; k < K; k += kQThreads) {
+    const int8_t v = sv[SMPQ_TRIAL_SAVE_HEADER + k];
+    codes[(size_t)c * K + k] = v;
+    if (km) km[((size_t)(k >> 6) * cout + c) * 64 + (k & 63)] = v;
+  }
+  if (threadIdx.x == 0) {
+    wscale[c] = reinterpret_cast<const float*>(sv)[0];
+    col_scale[c] = reinterpret_cast<const float*>(sv)[1];
+    if (offset) offset[c] = reinterpret_cast<const int32_t*>(sv)[2];
+  }
+}
+
 // ------------------------------------------------------------------------------------------
 // host twin (native C++, same arithmetic)
 // ------------------------------------------------------------------------------------------
@@ -590,5 +712,50 @@ extern "C" int smpq_trial_rows_restore_host(int cout, int K, const int32_t* chan
                                             int8_t* codes, float* wscale, float* col_scale, const void* save) {
   std::string err;
   const int rc = trial_rows_restore_host(cout, K, channels, n, wlimbs, codes, wscale, col_scale, save, &err);
+  return rc != SMPQ_OK ? fail(rc, err) : rc;
+}
+
+extern "C" int smpq_trial_rows_patch_x8(const float* w, int cout, int cin, int kh, int kw, const int32_t* channels,
+                                        const int32_t* bits, int n, int semantics, const float* bn_a, int8_t* codes,
+                                        int8_t* codes_km, int32_t* offset, float* wscale, float* col_scale, void* save,
+                                        int32_t* status, smpq_stream_t stream) {
+  std::string err;
+  const int rc = trial_rows_x8_check("smpq_trial_rows_patch_x8", w, cout, cin, kh, kw, channels, bits, n, semantics,
+                                     bn_a, codes, wscale, col_scale, save, status, &err);
+  if (rc != SMPQ_OK) return fail(rc, err);
+  const long long slot = SMPQ_TRIAL_SAVE_HEADER + (long long)cin * kh * kw;
+  hipLaunchKernelGGL(trial_rows_patch_x8_kernel, dim3(n), dim3(kQThreads), 0, (hipStream_t)stream, w, cout, cin,
+                     kh * kw, channels, bits, semantics, bn_a, codes, codes_km, offset, wscale, col_scale,
+                     static_cast<int8_t*>(save), slot, status);
+  return check_hip(hipGetLastError(), "trial_rows_patch_x8_kernel launch");
+}
+
+extern "C" int smpq_trial_rows_restore_x8(int cout, int K, const int32_t* channels, int n, int8_t* codes,
+                                          int8_t* codes_km, int32_t* offset, float* wscale, float* col_scale,
+                                          const void* save, smpq_stream_t stream) {
+  std::string err;
+  const int rc = trial_rows_restore_x8_check("smpq_trial_rows_restore_x8", cout, K, channels, n, codes, wscale,
+                                             col_scale, save, &err);
+  if (rc != SMPQ_OK) return fail(rc, err);
+  const long long slot = SMPQ_TRIAL_SAVE_HEADER + (long long)K;
+  hipLaunchKernelGGL(trial_rows_restore_x8_kernel, dim3(n), dim3(kQThreads), 0, (hipStream_t)stream, cout, K, channels,
+                     codes, codes_km, offset, wscale, col_scale, static_cast<const int8_t*>(save), slot);
+  return check_hip(hipGetLastError(), "trial_rows_restore_x8_kernel launch");
+}
+
+extern "C" int smpq_trial_rows_patch_x8_host(const float* w, int cout, int cin, int kh, int kw,
+                                             const int32_t* channels, const int32_t* bits, int n, int semantics,
+                                             const float* bn_a, int8_t* codes, int32_t* offset, float* wscale,
+                                             float* col_scale, void* save, int32_t* status) {
+  std::string err;
+  const int rc = trial_rows_patch_x8_host(w, cout, cin, kh, kw, channels, bits, n, semantics, bn_a, codes, offset,
+                                          wscale, col_scale, save, status, &err);
+  return rc != SMPQ_OK ? fail(rc, err) : rc;
+}
+
+extern "C" int smpq_trial_rows_restore_x8_host(int cout, int K, const int32_t* channels, int n, int8_t* codes,
+                                               int32_t* offset, float* wscale, float* col_scale, const void* save) {
+  std::string err;
+  const int rc = trial_rows_restore_x8_host(cout, K, channels, n, codes, offset, wscale, col_scale, save, &err);
   return rc != SMPQ_OK ? fail(rc, err) : rc;
 }

@@ -213,7 +213,7 @@ inline int trial_rows_restore_check(int cout, int K, const void* channels, int n
 
 // The lists themselves (host memory): every channel in range and seen once, every bit-width in 1..16.
 inline int trial_rows_lists_check(const char* fn, int cout, const int32_t* channels, const int32_t* bits, int n,
-                                  std::string* err) {
+                                  std::string* err, int maxbits = 16) {
   std::vector<char> seen((size_t)cout, 0);
   for (int i = 0; i < n; ++i) {
     const int c = channels[i];
@@ -221,8 +221,8 @@ inline int trial_rows_lists_check(const char* fn, int cout, const int32_t* chann
       *err = std::string(fn) + ": channel outside [0, cout)";
       return SMPQ_E_INVALID;
     }
-    if (bits && (bits[i] < 1 || bits[i] > 16)) {
-      *err = std::string(fn) + ": bits outside 1..16";
+    if (bits && (bits[i] < 1 || bits[i] > maxbits)) {
+      *err = std::string(fn) + ": bits outside 1.." + std::to_string(maxbits);
       return SMPQ_E_BITS;
     }
     if (seen[c]) {
@@ -259,6 +259,155 @@ inline int trial_rows_restore_host(int cout, int K, const int32_t* channels, int
     rc = trial_row_restore_host(cout, K, channels[i], wlimbs, codes, wscale, col_scale,
                                 static_cast<const int8_t*>(save) + i * slot, err);
     if (rc != SMPQ_OK) return rc;
+  }
+  return SMPQ_OK;
+}
+
+// ---- n rows of one exact8 operand (include/smpq.h, "trial rows patch, exact8 operands") -----------
+// One int8 plane, a per-channel offset (or none), wscale = the step. The arithmetic restates
+// quantize_row_host and pack_weights_ex_kernel (lw == 1) of quant.hip; quant.hip wraps these as
+// smpq_trial_rows_patch_x8_host / _restore_x8_host (tools/trial_rows_x8_sanitize.cpp).
+inline int trial_rows_x8_check(const char* fn, const void* w, int cout, int cin, int kh, int kw, const void* channels,
+                               const void* bits, int n, int semantics, const void* bn_a, const void* codes,
+                               const void* wscale, const void* col_scale, const void* save, const void* status,
+                               std::string* err) {
+  const std::string who(fn);
+  if (!w || !channels || !bits || !bn_a || !codes || !wscale || !col_scale || !save || !status) {
+    *err = who + ": null pointer";
+    return SMPQ_E_INVALID;
+  }
+  if (cout <= 0 || cin <= 0 || kh <= 0 || kw <= 0) {
+    *err = who + ": sizes must be positive";
+    return SMPQ_E_INVALID;
+  }
+  if (semantics != SMPQ_QSEM_CPU && semantics != SMPQ_QSEM_DEVICE) {
+    *err = who + ": semantics must be SMPQ_QSEM_CPU or SMPQ_QSEM_DEVICE";
+    return SMPQ_E_INVALID;
+  }
+  if ((uintptr_t)save & 3) {
+    *err = who + ": save area must be 4-byte aligned";
+    return SMPQ_E_INVALID;
+  }
+  if (n < 1 || n > cout) {
+    *err = who + ": n outside 1..cout";
+    return SMPQ_E_INVALID;
+  }
+  if (cin % 64 != 0 || (long long)cin * kh * kw > SMPQ_TRIAL_MAX_K) {
+    *err = who + ": cin must be a multiple of 64 and K at most SMPQ_TRIAL_MAX_K";
+    return SMPQ_E_SHAPE;
+  }
+  return SMPQ_OK;
+}
+
+inline int trial_rows_restore_x8_check(const char* fn, int cout, int K, const void* channels, int n, const void* codes,
+                                       const void* wscale, const void* col_scale, const void* save, std::string* err) {
+  const std::string who(fn);
+  if (!channels || !codes || !wscale || !col_scale || !save) {
+    *err = who + ": null pointer";
+    return SMPQ_E_INVALID;
+  }
+  if (cout <= 0 || K <= 0 || n < 1 || n > cout || ((uintptr_t)save & 3)) {
+    *err = who + ": need cout, K > 0, n in 1..cout, an aligned save area";
+    return SMPQ_E_INVALID;
+  }
+  if (K % 64 != 0 || K > SMPQ_TRIAL_MAX_K) {
+    *err = who + ": K must be a multiple of 64, at most SMPQ_TRIAL_MAX_K";
+    return SMPQ_E_SHAPE;
+  }
+  return SMPQ_OK;
+}
+
+// One row, arguments already checked: save, then the header's steps; a nonzero status leaves the
+// operand as it is.
+inline void trial_row_patch_x8_body_host(const float* w, int cin, int kh, int kw, int c, int bits, int semantics,
+                                         const float* bn_a, int8_t* codes, int32_t* offset, float* wscale,
+                                         float* col_scale, void* save, int32_t* status) {
+  const int taps = kh * kw, K = cin * taps;
+  const float* row = w + (size_t)c * K;
+  float* shead = static_cast<float*>(save);
+  int8_t* scodes = static_cast<int8_t*>(save) + SMPQ_TRIAL_SAVE_HEADER;
+  shead[0] = wscale[c];
+  shead[1] = col_scale[c];
+  const int32_t o_old = offset ? offset[c] : 0;
+  std::memcpy(static_cast<int8_t*>(save) + 8, &o_old, sizeof o_old);
+  std::memcpy(scodes, codes + (size_t)c * K, K);
+  float mn = INFINITY, mx = -INFINITY;
+  for (int i = 0; i < K; ++i) {
+    mn = std::fmin(mn, row[i]);
+    mx = std::fmax(mx, row[i]);
+  }
+  if (mx == mn) {
+    *status = 1;
+    return;
+  }
+  const double scale = ((double)mx - (double)mn) / (double)((1 << bits) - 1);
+  const double zd = std::nearbyint((double)mn / scale) + 0.0;
+  const float s = (float)scale;
+  const float z32 = (float)zd;
+  const float inv32 = (float)(1.0 / scale);
+  std::vector<int> m(K);
+  int mmin = INT32_MAX, mmax = INT32_MIN;
+  bool bad = !(s > 0.f);
+  for (int i = 0; i < K && !bad; ++i) {
+    const float d = semantics == SMPQ_QSEM_DEVICE ? row[i] * inv32 : row[i] / s;
+    const float v = (std::nearbyintf(d + z32) - z32) * s;
+    const float mf = std::nearbyintf(v / s);
+    if (mf * s != v || std::fabs(mf) > 32512.f) {
+      bad = true;
+      break;
+    }
+    m[i] = (int)mf;
+    mmin = mmin < m[i] ? mmin : m[i];
+    mmax = mmax > m[i] ? mmax : m[i];
+  }
+  if (bad || mmax - mmin > 255) {
+    *status = 3;
+    return;
+  }
+  const int o = (mmin < -128 || mmax > 127) ? mmin + 128 : 0;
+  if (o != 0 && !offset) {
+    *status = 4;
+    return;
+  }
+  for (int k = 0; k < K; ++k) {
+    const int tap = k / cin, ci = k - tap * cin;
+    codes[(size_t)c * K + k] = (int8_t)(m[ci * taps + tap] - o);
+  }
+  if (offset) offset[c] = o;
+  wscale[c] = s;
+  col_scale[c] = s * bn_a[c];
+}
+
+inline int trial_rows_patch_x8_host(const float* w, int cout, int cin, int kh, int kw, const int32_t* channels,
+                                    const int32_t* bits, int n, int semantics, const float* bn_a, int8_t* codes,
+                                    int32_t* offset, float* wscale, float* col_scale, void* save, int32_t* status,
+                                    std::string* err) {
+  const char* fn = "smpq_trial_rows_patch_x8";
+  int rc = trial_rows_x8_check(fn, w, cout, cin, kh, kw, channels, bits, n, semantics, bn_a, codes, wscale, col_scale,
+                               save, status, err);
+  if (rc == SMPQ_OK) rc = trial_rows_lists_check(fn, cout, channels, bits, n, err, 8);
+  if (rc != SMPQ_OK) return rc;
+  const size_t slot = SMPQ_TRIAL_SAVE_HEADER + (size_t)cin * kh * kw;
+  for (int i = 0; i < n; ++i)
+    trial_row_patch_x8_body_host(w, cin, kh, kw, channels[i], bits[i], semantics, bn_a, codes, offset, wscale,
+                                 col_scale, static_cast<int8_t*>(save) + i * slot, status + i);
+  return SMPQ_OK;
+}
+
+inline int trial_rows_restore_x8_host(int cout, int K, const int32_t* channels, int n, int8_t* codes, int32_t* offset,
+                                      float* wscale, float* col_scale, const void* save, std::string* err) {
+  const char* fn = "smpq_trial_rows_restore_x8";
+  int rc = trial_rows_restore_x8_check(fn, cout, K, channels, n, codes, wscale, col_scale, save, err);
+  if (rc == SMPQ_OK) rc = trial_rows_lists_check(fn, cout, channels, nullptr, n, err);
+  if (rc != SMPQ_OK) return rc;
+  const size_t slot = SMPQ_TRIAL_SAVE_HEADER + (size_t)K;
+  for (int i = 0; i < n; ++i) {
+    const int8_t* s = static_cast<const int8_t*>(save) + i * slot;
+    const int c = channels[i];
+    std::memcpy(codes + (size_t)c * K, s + SMPQ_TRIAL_SAVE_HEADER, K);
+    if (offset) std::memcpy(offset + c, s + 8, sizeof(int32_t));
+    wscale[c] = reinterpret_cast<const float*>(s)[0];
+    col_scale[c] = reinterpret_cast<const float*>(s)[1];
   }
   return SMPQ_OK;
 }

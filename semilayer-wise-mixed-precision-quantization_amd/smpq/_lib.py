@@ -98,6 +98,10 @@ _PROTOS = {
     "smpq_trial_rows_restore": (_i, [_i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "smpq_trial_rows_patch_host": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "smpq_trial_rows_restore_host": (_i, [_i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "smpq_trial_rows_patch_x8": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "smpq_trial_rows_restore_x8": (_i, [_i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "smpq_trial_rows_patch_x8_host": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "smpq_trial_rows_restore_x8_host": (_i, [_i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "smpq_u8lut_decode": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     "smpq_u8lut_encode": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "smpq_u8lut_decode_host": (_i, [_vp, _i, _i, _i, _vp, _vp]),

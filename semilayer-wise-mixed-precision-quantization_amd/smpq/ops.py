@@ -254,11 +254,12 @@ def trial_rows_save_bytes(wlimbs, K, n):
     return int(n) * trial_save_bytes(wlimbs, K)
 
 
-def trial_rows_lists(channels, bits, cout, device, what="trial_rows_patch"):
+def trial_rows_lists(channels, bits, cout, device, what="trial_rows_patch", max_bits=16):
     """The validated pair of lists of one rows patch on ``device``: TrialRows(channels int32 [n],
     bits int32 [n], n, cout). ``channels``: a sequence or host tensor, non-empty, each in [0, cout),
     pairwise distinct; ``bits``: one int for every row or a sequence of the same length, each in
-    1..16. One upload each; a sweep makes the pairs of a conv up front and passes them back in."""
+    1..``max_bits`` (8 for trial_rows_patch_x8). One upload each; a sweep makes the pairs of a conv up
+    front and passes them back in."""
     ch = torch.as_tensor(channels).reshape(-1)
     _req(not ch.is_cuda and not ch.is_floating_point() and ch.dtype != torch.bool,
          "%s: channels must be an integer sequence or host tensor" % what)
@@ -276,7 +277,7 @@ def trial_rows_lists(channels, bits, cout, device, what="trial_rows_patch"):
              "%s: bits must be an int, an integer sequence or a host tensor" % what)
         b = b.to(torch.int64)
         _req(b.numel() == n, "%s: channels and bits differ in length" % what)
-    _req(int(b.min()) >= 1 and int(b.max()) <= 16, "%s: bits outside 1..16" % what)
+    _req(int(b.min()) >= 1 and int(b.max()) <= int(max_bits), "%s: bits outside 1..%d" % (what, max_bits))
     return TrialRows(ch.to(torch.int32).contiguous().to(device), b.to(torch.int32).contiguous().to(device), n, int(cout))
 
 
@@ -330,6 +331,72 @@ def trial_rows_restore(channels, codes, wscale, col_scale, save, km=None):
                 col_scale, save)
     else:
         _launch_twin(codes, "smpq_trial_rows_restore", cout, K, rows.channels, rows.n, lw, codes, wscale, col_scale, save)
+
+
+# ---- trial rows patch, exact8 operands (include/smpq.h): rows of a fully quantized conv's operand -----
+def _trial_rows_x8_operand(what, codes, offset, wscale, col_scale, save, channels, bits, km):
+    """The checks of an exact8 operand (codes int8 [1, cout, K], ``offset`` int32 [cout] or None) for
+    the rows ``channels``: (cout, K, TrialRows)."""
+    _req(torch.is_tensor(codes) and codes.dtype == torch.int8 and codes.dim() == 3 and codes.is_contiguous()
+         and codes.shape[0] == 1, "%s: codes must be contiguous int8 [1, cout, K]" % what)
+    _, cout, K = codes.shape
+    dev = codes.device
+    _req(K % 64 == 0 and K <= TRIAL_MAX_K, "%s: K must be a multiple of 64, at most %d" % (what, TRIAL_MAX_K))
+    if isinstance(channels, TrialRows) or bits is None:  # (uploaded lists: made with max_bits=8 by the caller)
+        rows = _trial_rows(what, channels, bits, cout, dev)
+    else:
+        rows = trial_rows_lists(channels, bits, cout, dev, what, max_bits=8)
+    for name, t in (("wscale", wscale), ("col_scale", col_scale)):
+        _req(torch.is_tensor(t) and t.dtype == torch.float32 and t.numel() == cout and t.is_contiguous()
+             and t.device == dev, "%s: %s must be a contiguous fp32 [cout] tensor on the codes' device" % (what, name))
+    _req(offset is None or (torch.is_tensor(offset) and offset.dtype == torch.int32 and offset.shape == (cout,)
+                            and offset.is_contiguous() and offset.device == dev),
+         "%s: offset must be None or a contiguous int32 [cout] tensor on the codes' device" % what)
+    _req(torch.is_tensor(save) and save.dtype == torch.int8 and save.dim() == 1 and save.is_contiguous()
+         and save.device == dev and save.numel() >= trial_rows_save_bytes(1, K, rows.n) and save.data_ptr() % 4 == 0,
+         "%s: save must be a contiguous, 4-byte aligned int8 tensor of at least trial_rows_save_bytes(1, K, n)" % what)
+    if km is not None:
+        _req(dev.type == "cuda" and km.dtype == torch.int8 and km.shape == (1, K // 64, cout, 64)
+             and km.is_contiguous() and km.device == dev, "%s: K-major codes must be int8 [1, K/64, cout, 64]" % what)
+    return cout, K, rows
+
+
+def trial_rows_patch_x8(w, channels, bits, bn_a, codes, offset, wscale, col_scale, save, status, km=None,
+                        semantics=None):
+    """trial_rows_patch for an 'exact8' operand (``codes`` int8 [1, cout, K], ``offset`` int32 [cout]
+    or None, ``wscale`` = the steps): row i re-quantized at ``bits[i]`` <= 8 bits and coded as
+    pack_weights_ex(..., 1) would, in ONE launch (uploaded lists: trial_rows_lists(..., max_bits=8)).
+    ``status`` int32 [n], caller-zeroed: 1 constant row, 3 the row is off the grid or spans more than
+    256 levels, 4 the row needs an offset and ``offset`` is None; such a row stays as it is. Returns
+    the TrialRows, for the restore."""
+    what = "trial_rows_patch_x8"
+    _req(w.dtype == torch.float32 and w.dim() == 4 and w.is_contiguous(), "%s: need a contiguous fp32 4-D weight" % what)
+    cout, K, rows = _trial_rows_x8_operand(what, codes, offset, wscale, col_scale, save, channels, bits, km)
+    _req(w.device == codes.device and w.shape[0] == cout and w.shape[1] % 64 == 0
+         and w.shape[1] * w.shape[2] * w.shape[3] == K, "%s: weight and codes disagree" % what)
+    _req(bn_a.dtype == torch.float32 and bn_a.numel() == cout and bn_a.is_contiguous() and bn_a.device == w.device,
+         "%s: bn_a must be a contiguous fp32 [cout] tensor on the weight's device" % what)
+    _req(status.dtype == torch.int32 and status.dim() == 1 and status.is_contiguous() and status.numel() >= rows.n
+         and status.device == w.device, "%s: status must be a contiguous int32 [n] tensor on the weight's device" % what)
+    sem = _qsem(semantics, w.is_cuda)
+    head = (w, cout, int(w.shape[1]), int(w.shape[2]), int(w.shape[3]), rows.channels, rows.bits, rows.n, sem, bn_a, codes)
+    if w.is_cuda:
+        _launch(w.device, "smpq_trial_rows_patch_x8", *head, km, offset, wscale, col_scale, save, status)
+    else:
+        _launch_twin(w, "smpq_trial_rows_patch_x8", *head, offset, wscale, col_scale, save, status)
+    return rows
+
+
+def trial_rows_restore_x8(channels, codes, offset, wscale, col_scale, save, km=None):
+    """Put back what trial_rows_patch_x8 saved for the same ``channels`` (a sequence or its TrialRows)."""
+    what = "trial_rows_restore_x8"
+    cout, K, rows = _trial_rows_x8_operand(what, codes, offset, wscale, col_scale, save, channels, None, km)
+    if codes.is_cuda:
+        _launch(codes.device, "smpq_trial_rows_restore_x8", cout, K, rows.channels, rows.n, codes, km, offset, wscale,
+                col_scale, save)
+    else:
+        _launch_twin(codes, "smpq_trial_rows_restore_x8", cout, K, rows.channels, rows.n, codes, offset, wscale,
+                     col_scale, save)
 
 
 def image_quantize_s2d(x, x_absmax, limbs=None):

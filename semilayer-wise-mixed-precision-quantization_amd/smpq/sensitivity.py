@@ -91,6 +91,34 @@ def patchable_rows(conv, bn, channels):
     return bool(free.any())
 
 
+def patchable_rows_x8(conv, bn, channels, bits):
+    """Can a trial that RE-quantizes ``channels`` of a fully quantized ``conv`` at ``bits`` (one
+    int or one per channel) patch its 'exact8' operand in place (ops.trial_rows_patch_x8)? True when
+      * the conv has a ConvPlan whose codes are [1, cout, K] of kind 'exact8';
+      * the K-major copy on the codes is there exactly when ops.KMAJOR is on;
+      * K is a multiple of 64 within the patch kernel's row limit;
+      * every channel of the conv is quantized, so that it stays fully quantized whatever the
+        channels and the normal path would again pack one int8 plane;
+      * every bit-width is at most 8 (a wider row cannot be exact8).
+    Whether a ROW can then be coded (on the grid, within 256 levels, with an offset only where the
+    operand has offsets) is the kernel's answer, in its status words. codes, their K-major copy,
+    offset, wscale and the folded col_scale are all an exact8 operand is: the resident 1x1 tiles, the
+    halo 3x3 tiles and the chained conv3 / conv1 launches read these same tensors."""
+    if not isinstance(conv, QConv2d):
+        return False
+    plan = engine.conv_plan(conv, bn)
+    if plan is None or getattr(plan, "kind", None) != "exact8" or plan.codes.dim() != 3 or plan.codes.shape[0] != 1:
+        return False
+    if (getattr(plan.codes, "_smpq_km", None) is not None) != bool(ops.KMAJOR[0]):
+        return False
+    if plan.codes.shape[2] % 64 != 0 or plan.codes.shape[2] > ops.TRIAL_MAX_K:
+        return False
+    if not conv.fully_quantized():
+        return False
+    bits = [bits] if isinstance(bits, (int, np.integer)) else list(bits)
+    return len([int(c) for c in channels]) > 0 and all(1 <= int(b) <= 8 for b in bits)
+
+
 def arch_of(net):
     blocks = assignments.blocks_of(net)
     if hasattr(blocks[0], "conv3"):
