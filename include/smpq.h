@@ -642,6 +642,65 @@ int smpq_trial_rows_patch_x8_host(const float* w, int cout, int cin, int kh, int
 int smpq_trial_rows_restore_x8_host(int cout, int K, const int32_t* channels, int n, int8_t* codes, int32_t* offset,
                                     float* wscale, float* col_scale, const void* save);
 
+/* ---- trial rows conv: a few output channels of one conv, into limb planes we hold (normative) -----
+ * A per-channel trial of a block's LAST conv changes one channel of that conv's output, which is the
+ * next block's input: a tensor the sensitivity table already keeps (smpq/suffix.py). Instead of
+ * running the block again, smpq_trial_rows_conv_q computes the listed output channels of the conv
+ * from its (patched) operand and writes them in place into the kept limb planes, after saving the
+ * bytes it replaces; smpq_trial_rows_conv_restore puts those bytes back. Additions to ABI 7.
+ *
+ * The conv is smpq_conv2d_fwd_q in its static limb-plane output mode (y == NULL, yq and yq_range
+ * given, no fp32 residual, no y_absmax) with ReLU on, wlimbs >= 2 and no offsets:
+ *   xq [limbs][n][h][w][cin], x_absmax [n]; codes [wlimbs][cout][K] row-major (k = tap*cin + ci);
+ *   col_scale, col_shift [cout]; residual_q [limbs][n*h*w][cout] with residual_range, or NULL;
+ *   yq [limbs][n*h*w][cout], updated in place; yq_range > 0; overflow int32 [1].
+ * Geometries: 1x1 / stride 1 / pad 0 and 3x3 / stride 1 / pad 1 (output pixels = input pixels,
+ * M = n*h*w), cin % 64 == 0, K = kh*kw*cin <= SMPQ_TRIAL_MAX_K, cout % 16 == 0, limbs 2 or 3,
+ * wlimbs 2 or 3 (3 with limbs == 3 only).
+ *   channels  int32 [nrows], 1 <= nrows <= cout, pairwise distinct, device memory for the device
+ *             entry point (range and distinctness are THE CALLER'S DUTY there, smpq/ops.py checks
+ *             them before the upload; an entry outside [0, cout) is skipped); the *_host twins
+ *             check the list themselves (SMPQ_E_INVALID)
+ *   save      nrows slots of limbs*M bytes: slot i holds channel channels[i]'s old digit bytes,
+ *             byte l*M + m for limb l of pixel m. Each byte is saved before it is overwritten.
+ * Per listed channel c and output pixel m (image g), IEEE fp32, no contraction:
+ *   1. acc_s = the exact int32 sum over k and over the limb pairs (la, lw) with la + lw - SMIN == s
+ *      of x_digit_la(m, k) * w_digit_lw(c, k), SMIN = max(0, limbs + wlimbs - 4), for the
+ *      NACC = limbs + wlimbs - 1 - SMIN values of s: the pairs with la + lw < SMIN are skipped, as
+ *      the conv kernels skip them. A 3x3 tap outside the image contributes zero. The int32 bound is
+ *      the conv's (K <= SMPQ_TRIAL_MAX_K).
+ *   2. v = (float)acc_0 [* 256^SMIN when SMIN > 0], then v = fmaf((float)acc_s, 256^(SMIN + s), v)
+ *      for s = 1 .. NACC-1.
+ *   3. inv = QMAX / yq_range; z = fmaf(v, (x_absmax[g] * (1 / QMAX)) * (col_scale[c] * inv),
+ *      col_shift[c] * inv); with a residual z = fmaf((float)r, (residual_range / QMAX) * inv, z),
+ *      r = the residual's code at (m, c). QMAX = 32512 (limbs 2) or 8323072 (limbs 3).
+ *   4. zr = rintf(z); overflow[0] is set to 1 when zr > QMAX, exactly when the conv would;
+ *      code = min(max(zr, 0), QMAX), written as `limbs` balanced base-256 digits, low first.
+ * These are the conv kernels' own operations (csrc/lds_dma.h lean_v1 / lean_zr / lean_clamp), so the listed
+ * channels come out bit for bit as a full smpq_conv2d_fwd_q launch would write them; every other
+ * byte of yq is left alone. Grid: (pixel tiles of 64) x rows, 256 threads, the row's wlimbs*K weight
+ * bytes staged once in LDS, activations read in 16-byte pieces, v_dot4_i32_i8 accumulation; all
+ * stores are plain vector stores.
+ * Return codes, before any launch or write: SMPQ_E_INVALID for a null pointer (residual_q alone may
+ * be NULL), limbs or wlimbs outside 2..3 (or wlimbs 3 with limbs 2), nrows outside 1..cout, a range
+ * that is not > 0, xq or codes not 16-byte aligned; SMPQ_E_SHAPE for another geometry, non-positive
+ * sizes, cin % 64 != 0, K > SMPQ_TRIAL_MAX_K, cout % 16 != 0 or n*h*w >= 2^31. */
+int smpq_trial_rows_conv_q(const int8_t* xq, const float* x_absmax, int n, int h, int w, int cin, const int8_t* codes,
+                           int wlimbs, int cout, int kh, int kw, int stride, int pad, const float* col_scale,
+                           const float* col_shift, int limbs, const int8_t* residual_q, float residual_range,
+                           const int32_t* channels, int nrows, int8_t* yq, float yq_range, int32_t* overflow,
+                           void* save, smpq_stream_t stream);
+/* pixels = n*h*w of the patched call; writes every slot back. */
+int smpq_trial_rows_conv_restore(const int32_t* channels, int nrows, int limbs, int64_t pixels, int cout, int8_t* yq,
+                                 const void* save, smpq_stream_t stream);
+int smpq_trial_rows_conv_q_host(const int8_t* xq, const float* x_absmax, int n, int h, int w, int cin,
+                                const int8_t* codes, int wlimbs, int cout, int kh, int kw, int stride, int pad,
+                                const float* col_scale, const float* col_shift, int limbs, const int8_t* residual_q,
+                                float residual_range, const int32_t* channels, int nrows, int8_t* yq, float yq_range,
+                                int32_t* overflow, void* save);
+int smpq_trial_rows_conv_restore_host(const int32_t* channels, int nrows, int limbs, int64_t pixels, int cout,
+                                      int8_t* yq, const void* save);
+
 /* Diagnostics: one v_mfma_i32_16x16x64_i8 with the kernel's fragment mapping.
  *   a [16][64] int8 row-major, b [16][64] int8 (b[col][k]), c [16][16] int32 row-major */
 int smpq_debug_mfma_i8(const int8_t* a, const int8_t* b, int32_t* c, smpq_stream_t stream);

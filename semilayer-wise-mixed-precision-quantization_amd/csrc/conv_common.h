@@ -59,6 +59,13 @@ __device__ __host__ constexpr float act_qmax() {
   return L == 1 ? 127.f : (L == 2 ? 32512.f : 8323072.f);
 }
 
+// The (activation limb la, weight limb lw) passes every conv kernel keeps: those with
+// la + lw >= limb_smin(L, LW) (the products of two low digits are below the output's resolution when
+// both sides are wide); pass (la, lw) adds into int32 accumulator la + lw - SMIN of limb_nacc(L, LW),
+// whose weight is 256^(la + lw). The one-row trial conv (trial_conv.hip) forms the same sums.
+constexpr int limb_smin(int L, int LW) { return (L + LW - 4) > 0 ? (L + LW - 4) : 0; }
+constexpr int limb_nacc(int L, int LW) { return L + LW - 1 - limb_smin(L, LW); }
+
 template <int L>
 __device__ __forceinline__ void split_limbs(int q, int* d) {
   // balanced base-256 digits, each in [-128, 127]

@@ -93,8 +93,8 @@ __device__ __forceinline__ void qconv_glds_body(ConvArgs a, int bid, int total, 
   constexpr int NW = WAVES_C * WAVES_P;
   constexpr int BC = 16 * WC * WAVES_C;  // channels per block tile
   constexpr int BP = 16 * WP * WAVES_P;  // pixels per block tile
-  constexpr int SMIN = (L + LW - 4) > 0 ? (L + LW - 4) : 0;
-  constexpr int NACC = L + LW - 1 - SMIN;
+  constexpr int SMIN = limb_smin(L, LW);
+  constexpr int NACC = limb_nacc(L, LW);
   constexpr int KH = BK / 64;      // MFMA K steps per stage
   constexpr int RPP = 1024 / BK;   // rows per 1-KiB DMA piece
   constexpr int CPR = BK / 16;     // 16-B chunks per row
@@ -881,8 +881,7 @@ constexpr GldsCfg kGlds[] = {
 template <int L, int LW, int WAVES_C, int WAVES_P, int WC, int WP, bool S2D = false, int NST = 2, int MINW = 2,
           int BK = 64, bool PIPE = false>
 static int launch_one(const ConvArgs& a, hipStream_t stream) {
-  constexpr int SMIN = (L + LW - 4) > 0 ? (L + LW - 4) : 0;
-  if constexpr ((L + LW - 1 - SMIN) * WC * WP * 4 > 128) {
+  if constexpr (limb_nacc(L, LW) * WC * WP * 4 > 128) {
     return fail(SMPQ_E_INVALID, "smpq_conv2d_fwd: tile config too large for these limb counts");
   } else {
     constexpr int BC = 16 * WC * WAVES_C, BP = 16 * WP * WAVES_P;

@@ -84,8 +84,8 @@ __device__ __forceinline__ int ach(int c, int r) {
 template <int L, int LW, int KC, int CW, int WP, bool RES, int CW2 = 0, int LWD = 0, bool OFF = false,
           int KCD = KC>
 struct ResShape {
-  static constexpr int SMIN = (L + LW - 4) > 0 ? (L + LW - 4) : 0;
-  static constexpr int NACC = L + LW - 1 - SMIN;
+  static constexpr int SMIN = limb_smin(L, LW);
+  static constexpr int NACC = limb_nacc(L, LW);
   static constexpr int BN = 64 * CW, BP = 16 * WP, K = 64 * KC;
   static constexpr int ATILE = L * BP * K;                     // activation tile bytes
   static constexpr int ATILE_D = LWD > 0 ? L * BP * 64 * KCD : 0;  // the fused downsample's tile

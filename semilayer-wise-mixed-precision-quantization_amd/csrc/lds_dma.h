@@ -131,18 +131,42 @@ typedef float f2 __attribute__((ext_vector_type(2)));
 // lean_codes: the same, returning the clamped codes themselves (the fused stem + max pool pools
 // them before encoding).
 // lean_codes_v: the same from the recombined v (the limb-outer K loop folds its limbs itself).
+// lean_zr / lean_clamp / lean_v1: the per-element bodies of lean_codes_v and lean_codes; the one-row
+// trial conv (trial_conv.hip) calls them for its single channel, so its codes are the conv kernels'
+// bit for bit. lean_zr is rne(z) (the overflow test looks at it before the clamp), lean_clamp the code.
+__device__ __forceinline__ float lean_zr(float v, float rscale, float csq, float shq, bool has_res, const int* rqv,
+                                         int r, float rsq) {
+  float z = __fmaf_rn(v, rscale * csq, shq);
+  if (has_res) z = __fmaf_rn((float)rqv[r], rsq, z);
+  return rintf(z);
+}
+
+template <int L>
+__device__ __forceinline__ int lean_clamp(float zr, float lo) {
+  constexpr float qmax = act_qmax<L>();
+  return (int)__builtin_amdgcn_fmed3f(zr, lo, qmax);
+}
+
+// element r of the accumulator quads accs[0 .. NACC-1], recombined
+template <int NACC, int SMIN>
+__device__ __forceinline__ float lean_v1(const v4i* accs, int r) {
+  constexpr float w0 = SMIN == 0 ? 1.f : (SMIN == 1 ? 256.f : 65536.f);
+  float v = (float)accs[0][r];
+  if (SMIN != 0) v = v * w0;
+#pragma unroll
+  for (int t = 1; t < NACC; ++t) v = __fmaf_rn((float)accs[t][r], w0 * (float)(1 << (8 * t)), v);
+  return v;
+}
+
 template <int L>
 __device__ __forceinline__ float lean_codes_v(const float* vs, float rscale, const float* csq, const float* shq,
                                               bool has_res, const int* rqv, float rsq, bool relu, float lo, int* q) {
-  constexpr float qmax = act_qmax<L>();
   float m = 0.f;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    float z = __fmaf_rn(vs[r], rscale * csq[r], shq[r]);
-    if (has_res) z = __fmaf_rn((float)rqv[r], rsq, z);
-    const float zr = rintf(z);
+    const float zr = lean_zr(vs[r], rscale, csq[r], shq[r], has_res, rqv, r, rsq);
     m = fmaxf(m, relu ? zr : fabsf(zr));
-    q[r] = (int)__builtin_amdgcn_fmed3f(zr, lo, qmax);
+    q[r] = lean_clamp<L>(zr, lo);
   }
   return m;
 }
@@ -150,16 +174,9 @@ __device__ __forceinline__ float lean_codes_v(const float* vs, float rscale, con
 template <int L, int NACC, int SMIN>
 __device__ __forceinline__ float lean_codes(const v4i* accs, float rscale, const float* csq, const float* shq,
                                             bool has_res, const int* rqv, float rsq, bool relu, float lo, int* q) {
-  constexpr float w0 = SMIN == 0 ? 1.f : (SMIN == 1 ? 256.f : 65536.f);
   float vs[4];
 #pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    float v = (float)accs[0][r];
-    if (SMIN != 0) v = v * w0;
-#pragma unroll
-    for (int t = 1; t < NACC; ++t) v = __fmaf_rn((float)accs[t][r], w0 * (float)(1 << (8 * t)), v);
-    vs[r] = v;
-  }
+  for (int r = 0; r < 4; ++r) vs[r] = lean_v1<NACC, SMIN>(accs, r);
   return lean_codes_v<L>(vs, rscale, csq, shq, has_res, rqv, rsq, relu, lo, q);
 }
 

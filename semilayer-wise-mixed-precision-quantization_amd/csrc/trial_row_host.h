@@ -3,6 +3,7 @@
 // quant.hip wraps them as smpq_trial_row_patch_host / smpq_trial_row_restore_host and, for n rows of
 // one operand (tools/trial_rows_sanitize.cpp), smpq_trial_rows_patch_host / _restore_host. The arithmetic
 // restates quantize_row_host and pack_weights_ex_kernel (lw >= 2) of quant.hip; FP contraction off.
+// At the end: the twins of the trial rows conv (trial_conv.hip wraps them).
 #pragma once
 
 #include <cmath>
@@ -409,6 +410,151 @@ inline int trial_rows_restore_x8_host(int cout, int K, const int32_t* channels, 
     wscale[c] = reinterpret_cast<const float*>(s)[0];
     col_scale[c] = reinterpret_cast<const float*>(s)[1];
   }
+  return SMPQ_OK;
+}
+
+// ---- trial rows conv: listed output channels of one conv into held limb planes ---------------------
+// (include/smpq.h, "trial rows conv"). quant.hip's neighbour trial_conv.hip wraps the twins as
+// smpq_trial_rows_conv_q_host / _restore_host (tools/trial_rows_conv_sanitize.cpp). The arithmetic
+// restates lean_v1 / lean_zr / lean_clamp of lds_dma.h with <cmath>; FP contraction off.
+inline int trial_rows_conv_check(const char* fn, const void* xq, const void* x_absmax, int n, int h, int w, int cin,
+                                 const void* codes, int wlimbs, int cout, int kh, int kw, int stride, int pad,
+                                 const void* col_scale, const void* col_shift, int limbs, const void* residual_q,
+                                 float residual_range, const void* channels, int nrows, const void* yq,
+                                 float yq_range, const void* overflow, const void* save, std::string* err) {
+  const std::string who(fn);
+  if (!xq || !x_absmax || !codes || !col_scale || !col_shift || !channels || !yq || !overflow || !save) {
+    *err = who + ": null pointer";
+    return SMPQ_E_INVALID;
+  }
+  if (limbs < 2 || limbs > 3 || wlimbs < 2 || wlimbs > 3 || (wlimbs == 3 && limbs != 3)) {
+    *err = who + ": limbs and wlimbs must be 2 or 3 (3 weight limbs with 3 activation limbs only)";
+    return SMPQ_E_INVALID;
+  }
+  if (!(yq_range > 0.f) || (residual_q && !(residual_range > 0.f))) {
+    *err = who + ": ranges must be > 0";
+    return SMPQ_E_INVALID;
+  }
+  if (((uintptr_t)xq | (uintptr_t)codes) & 15) {
+    *err = who + ": xq and codes must be 16-byte aligned";
+    return SMPQ_E_INVALID;
+  }
+  if (n <= 0 || h <= 0 || w <= 0 || cin <= 0 || cout <= 0) {
+    *err = who + ": sizes must be positive";
+    return SMPQ_E_SHAPE;
+  }
+  if (nrows < 1 || nrows > cout) {
+    *err = who + ": nrows outside 1..cout";
+    return SMPQ_E_INVALID;
+  }
+  const bool k1 = kh == 1 && kw == 1 && stride == 1 && pad == 0, k3 = kh == 3 && kw == 3 && stride == 1 && pad == 1;
+  if (!k1 && !k3) {
+    *err = who + ": only 1x1 / stride 1 / pad 0 and 3x3 / stride 1 / pad 1";
+    return SMPQ_E_SHAPE;
+  }
+  if (cin % 64 != 0 || (long long)cin * kh * kw > SMPQ_TRIAL_MAX_K || cout % 16 != 0) {
+    *err = who + ": cin must be a multiple of 64, K at most SMPQ_TRIAL_MAX_K, cout a multiple of 16";
+    return SMPQ_E_SHAPE;
+  }
+  if ((long long)n * h * w > 0x7fffffffLL) {
+    *err = who + ": more than 2^31 - 1 pixels";
+    return SMPQ_E_SHAPE;
+  }
+  return SMPQ_OK;
+}
+
+inline int trial_rows_conv_restore_check(const char* fn, const void* channels, int nrows, int limbs, long long pixels,
+                                         int cout, const void* yq, const void* save, std::string* err) {
+  const std::string who(fn);
+  if (!channels || !yq || !save) {
+    *err = who + ": null pointer";
+    return SMPQ_E_INVALID;
+  }
+  if (limbs < 2 || limbs > 3 || cout <= 0 || nrows < 1 || nrows > cout) {
+    *err = who + ": need limbs 2 or 3, cout > 0, nrows in 1..cout";
+    return SMPQ_E_INVALID;
+  }
+  if (pixels <= 0 || pixels > 0x7fffffffLL) {
+    *err = who + ": pixels outside 1..2^31 - 1";
+    return SMPQ_E_SHAPE;
+  }
+  return SMPQ_OK;
+}
+
+inline int trial_rows_conv_host(const int8_t* xq, const float* x_absmax, int n, int h, int w, int cin,
+                                const int8_t* codes, int wlimbs, int cout, int kh, int kw, int stride, int pad,
+                                const float* col_scale, const float* col_shift, int limbs, const int8_t* residual_q,
+                                float residual_range, const int32_t* channels, int nrows, int8_t* yq, float yq_range,
+                                int32_t* overflow, void* save, std::string* err) {
+  const char* fn = "smpq_trial_rows_conv_q";
+  int rc = trial_rows_conv_check(fn, xq, x_absmax, n, h, w, cin, codes, wlimbs, cout, kh, kw, stride, pad, col_scale,
+                                 col_shift, limbs, residual_q, residual_range, channels, nrows, yq, yq_range, overflow,
+                                 save, err);
+  if (rc == SMPQ_OK) rc = trial_rows_lists_check(fn, cout, channels, nullptr, nrows, err);
+  if (rc != SMPQ_OK) return rc;
+  const int K = cin * kh * kw, L = limbs, LW = wlimbs;
+  const int smin = (L + LW - 4) > 0 ? (L + LW - 4) : 0, nacc = L + LW - 1 - smin;
+  const long long M = (long long)n * h * w, plane = M * cin, oplane = M * cout, wplane = (long long)cout * K;
+  const float qmax = L == 2 ? 32512.f : 8323072.f;
+  const float inv = qmax / yq_range, inv_qmax = 1.f / qmax;
+  const float rsq = residual_q ? (residual_range / qmax) * inv : 0.f;
+  const float w0 = smin == 0 ? 1.f : (smin == 1 ? 256.f : 65536.f);
+  int8_t* sv = static_cast<int8_t*>(save);
+  for (int i = 0; i < nrows; ++i) {
+    const int c = channels[i];
+    const float csq = col_scale[c] * inv, shq = col_shift[c] * inv;
+    for (long long m = 0; m < M; ++m) {
+      const int g = (int)(m / ((long long)h * w)), rem = (int)(m - (long long)g * h * w), oy = rem / w, ox = rem - oy * w;
+      int32_t acc[3] = {0, 0, 0};
+      for (int tap = 0; tap < kh * kw; ++tap) {
+        const int iy = oy + tap / kw - pad, ix = ox + tap % kw - pad;
+        if (iy < 0 || iy >= h || ix < 0 || ix >= w) continue;
+        const long long src = (((long long)g * h + iy) * w + ix) * cin;
+        for (int la = 0; la < L; ++la)
+          for (int lw = 0; lw < LW; ++lw) {
+            if (la + lw < smin) continue;
+            const int8_t* xp = xq + la * plane + src;
+            const int8_t* wp = codes + lw * wplane + (long long)c * K + (long long)tap * cin;
+            int32_t s = 0;
+            for (int k = 0; k < cin; ++k) s += (int32_t)xp[k] * (int32_t)wp[k];
+            acc[la + lw - smin] += s;
+          }
+      }
+      float v = (float)acc[0];
+      if (smin != 0) v = v * w0;
+      for (int t = 1; t < nacc; ++t) v = std::fmaf((float)acc[t], w0 * (float)(1 << (8 * t)), v);
+      float z = std::fmaf(v, (x_absmax[g] * inv_qmax) * csq, shq);
+      if (residual_q) {
+        int32_t r = 0;
+        for (int l = L - 1; l >= 0; --l) r = r * 256 + (int32_t)residual_q[l * oplane + m * cout + c];
+        z = std::fmaf((float)r, rsq, z);
+      }
+      const float zr = std::nearbyintf(z);
+      if (zr > qmax) *overflow = 1;
+      int q = (int)std::fmin(std::fmax(zr, 0.f), qmax);
+      for (int l = 0; l < L; ++l) {
+        const int lo = (l == L - 1) ? q : ((q + 128) & 255) - 128;
+        int8_t* dst = yq + l * oplane + m * cout + c;
+        sv[((long long)i * L + l) * M + m] = *dst;
+        *dst = (int8_t)lo;
+        q = (q - lo) >> 8;
+      }
+    }
+  }
+  return SMPQ_OK;
+}
+
+inline int trial_rows_conv_restore_host(const int32_t* channels, int nrows, int limbs, long long pixels, int cout,
+                                        int8_t* yq, const void* save, std::string* err) {
+  const char* fn = "smpq_trial_rows_conv_restore";
+  int rc = trial_rows_conv_restore_check(fn, channels, nrows, limbs, pixels, cout, yq, save, err);
+  if (rc == SMPQ_OK) rc = trial_rows_lists_check(fn, cout, channels, nullptr, nrows, err);
+  if (rc != SMPQ_OK) return rc;
+  const int8_t* sv = static_cast<const int8_t*>(save);
+  for (int i = 0; i < nrows; ++i)
+    for (int l = 0; l < limbs; ++l)
+      for (long long m = 0; m < pixels; ++m)
+        yq[((long long)l * pixels + m) * cout + channels[i]] = sv[((long long)i * limbs + l) * pixels + m];
   return SMPQ_OK;
 }
 

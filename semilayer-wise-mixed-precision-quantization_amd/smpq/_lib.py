@@ -102,6 +102,12 @@ _PROTOS = {
     "smpq_trial_rows_restore_x8": (_i, [_i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "smpq_trial_rows_patch_x8_host": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "smpq_trial_rows_restore_x8_host": (_i, [_i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "smpq_trial_rows_conv_q": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp,
+                                    ctypes.c_float, _vp, _i, _vp, ctypes.c_float, _vp, _vp, _vp]),
+    "smpq_trial_rows_conv_restore": (_i, [_vp, _i, _i, _i64, _i, _vp, _vp, _vp]),
+    "smpq_trial_rows_conv_q_host": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp,
+                                         ctypes.c_float, _vp, _i, _vp, ctypes.c_float, _vp, _vp]),
+    "smpq_trial_rows_conv_restore_host": (_i, [_vp, _i, _i, _i64, _i, _vp, _vp]),
     "smpq_u8lut_decode": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     "smpq_u8lut_encode": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "smpq_u8lut_decode_host": (_i, [_vp, _i, _i, _i, _vp, _vp]),

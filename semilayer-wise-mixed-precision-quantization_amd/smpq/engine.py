@@ -328,11 +328,12 @@ def _ds_fuse_plan(blk, x, ctx):
     return pd
 
 
-def block_forward(blk, x, ctx=None, last=False, t1=None, nxt=None):
+def block_forward(blk, x, ctx=None, last=False, t1=None, nxt=None, keep=None):
     """One BasicBlock / Bottleneck on an Act; returns (output Act, the next block's conv1 output
     Act or None). ``t1``: this block's conv1 output when the previous block already computed it
     (chain launch); ``nxt``: the next block, whose conv1 is chained onto this block's conv3 when
-    _pair_plan allows. In static mode no
+    _pair_plan allows. ``keep`` (a dict, default None): receives the last conv's input and identity
+    Acts (_keep_last_conv; smpq.suffix's rows route), never on a chain launch. In static mode no
     activation is stored in fp32 except the downsample's identity and the last block's output
     (avgpool): the identity of a block without downsample is read from its input's limb planes.
 
@@ -422,12 +423,26 @@ def block_forward(blk, x, ctx=None, last=False, t1=None, nxt=None):
                 nxt.conv1.last_path = "hip-%s-chain" % p1.kind
                 nt1 = Act(q=yq1, amax=ctx.range_tensor(nxt.conv1), rng=nxtarg.rng)
             return Act(q=yq3, amax=am3, rng=rng3), nt1
-        return run_conv(blk.conv3, blk.bn3, t2, True, residual=identity, ctx=ctx, want_amax=out_amax,
-                        want_f32=last), None
+        out = run_conv(blk.conv3, blk.bn3, t2, True, residual=identity, ctx=ctx, want_amax=out_amax, want_f32=last)
+        _keep_last_conv(keep, t2, identity, out)
+        return out, None
     # BasicBlock (resnet.py:55-68)
     join()
-    return run_conv(blk.conv2, blk.bn2, t1, True, residual=identity, ctx=ctx, want_amax=out_amax,
-                    want_f32=last), None
+    out = run_conv(blk.conv2, blk.bn2, t1, True, residual=identity, ctx=ctx, want_amax=out_amax, want_f32=last)
+    _keep_last_conv(keep, t1, identity, out)
+    return out, None
+
+
+def _keep_last_conv(keep, x, identity, out):
+    """block_forward's tap (``keep``: a dict or None): the Act fed to the block's last conv and the
+    identity Act, stored only when that conv ran as one plain launch in static mode (its output is limb
+    planes with a static range and nothing else) from limb planes with a limb-plane identity."""
+    if keep is None:
+        return
+    planes = all(isinstance(a, Act) and a.f32 is None and a.q is not None and a.rng is not None and a.amax is not None
+                 for a in (x, identity, out))
+    if planes:
+        keep["x"], keep["identity"] = x, identity
 
 
 def stem_s2d_plan(conv, bn):

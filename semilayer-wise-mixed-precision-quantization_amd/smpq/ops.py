@@ -399,6 +399,78 @@ def trial_rows_restore_x8(channels, codes, offset, wscale, col_scale, save, km=N
                      col_scale, save)
 
 
+# ---- trial rows conv (include/smpq.h): listed output channels of one conv into held limb planes -----
+def trial_rows_conv_save_bytes(L, pixels, nrows):
+    """Bytes of the save area of trial_rows_conv: ``nrows`` slots of L * pixels digit bytes."""
+    return int(nrows) * int(L) * int(pixels)
+
+
+def _trial_rows_conv_planes(what, yq, save, channels):
+    """The checks of the held planes ``yq`` [L, n, ho, wo, cout], the save area and the list:
+    (L, pixels, cout, TrialRows)."""
+    _req(torch.is_tensor(yq) and yq.dtype == torch.int8 and yq.dim() == 5 and yq.is_contiguous()
+         and yq.shape[0] in (2, 3), "%s: yq must be contiguous int8 [L, n, ho, wo, cout] with L 2 or 3" % what)
+    L, n, ho, wo, cout = yq.shape
+    rows = _trial_rows(what, channels, None, cout, yq.device)
+    _req(torch.is_tensor(save) and save.dtype == torch.int8 and save.dim() == 1 and save.is_contiguous()
+         and save.device == yq.device and save.numel() >= trial_rows_conv_save_bytes(L, n * ho * wo, rows.n),
+         "%s: save must be a contiguous int8 tensor of at least trial_rows_conv_save_bytes(L, pixels, n)" % what)
+    return L, n * ho * wo, cout, rows
+
+
+def trial_rows_conv(xq, x_absmax, codes, kh, kw, stride, pad, col_scale, col_shift, channels, yq, emit_range,
+                    overflow, save, residual_q=None, residual_range=None):
+    """The output channels ``channels`` (distinct; a sequence or the TrialRows of trial_rows_lists) of
+    conv2d_q(xq, x_absmax, codes, None, kh, kw, stride, pad, col_scale, col_shift, relu=True,
+    emit_range=..., want_f32=False, residual_q=..., residual_range=...) written IN PLACE into the held
+    output planes ``yq`` [L, n, h, w, cout], bit for bit what that launch would write there; every other
+    byte of ``yq`` stays. The replaced digit bytes go to ``save`` (int8
+    [trial_rows_conv_save_bytes(L, n*h*w, nrows)]) first; ``overflow`` (int32 [1]) is set exactly when
+    the conv would set it for these channels. ``codes`` int8 [LW, cout, K] row-major with LW >= 2 (no
+    offsets); 1x1 / stride 1 / pad 0 or 3x3 / stride 1 / pad 1, cin % 64 == 0, K <= TRIAL_MAX_K, L 2 or
+    3. Device tensors: one launch on the current stream, no host sync; host tensors: the native twin.
+    Returns the TrialRows, for the restore."""
+    what = "trial_rows_conv"
+    _req(torch.is_tensor(xq) and xq.dtype == torch.int8 and xq.dim() == 5 and xq.is_contiguous(),
+         "%s: xq must be contiguous int8 [L, n, h, w, cin]" % what)
+    L, pixels, cout, rows = _trial_rows_conv_planes(what, yq, save, channels)
+    limbs, n, h, w, cin = xq.shape
+    dev = xq.device
+    _req(limbs == L and yq.shape[1:4] == (n, h, w) and yq.device == dev, "%s: xq and yq disagree" % what)
+    _req((kh, kw, stride, pad) in ((1, 1, 1, 0), (3, 3, 1, 1)),
+         "%s: only 1x1 / stride 1 / pad 0 and 3x3 / stride 1 / pad 1" % what)
+    _req(torch.is_tensor(codes) and codes.dtype == torch.int8 and codes.dim() == 3 and codes.is_contiguous()
+         and codes.shape[0] in (2, 3) and codes.device == dev and (codes.shape[0] < 3 or L == 3),
+         "%s: codes must be contiguous int8 [LW, cout, K] with LW 2 or 3 (3 with L = 3 only)" % what)
+    lw, cout_w, K = codes.shape
+    _req(cout_w == cout and K == kh * kw * cin, "%s: codes and planes disagree" % what)
+    _req(cin % 64 == 0 and K <= TRIAL_MAX_K and cout % 16 == 0,
+         "%s: cin must be a multiple of 64, K at most %d, cout a multiple of 16" % (what, TRIAL_MAX_K))
+    _req(xq.data_ptr() % 16 == 0 and codes.data_ptr() % 16 == 0, "%s: xq and codes must be 16-byte aligned" % what)
+    _req(x_absmax.dtype == torch.float32 and x_absmax.numel() == n and x_absmax.is_contiguous()
+         and x_absmax.device == dev, "%s: x_absmax" % what)
+    for t in (col_scale, col_shift):
+        _req(t.dtype == torch.float32 and t.numel() == cout and t.is_contiguous() and t.device == dev,
+             "%s: col vectors" % what)
+    _req(emit_range is not None and emit_range > 0, "%s: emit_range must be > 0" % what)
+    _req(torch.is_tensor(overflow) and overflow.dtype == torch.int32 and overflow.numel() >= 1
+         and overflow.device == dev, "%s: overflow" % what)
+    if residual_q is not None:
+        _req(residual_q.shape == yq.shape and residual_q.dtype == torch.int8 and residual_q.is_contiguous()
+             and residual_q.device == dev and residual_range is not None and residual_range > 0,
+             "%s: residual_q" % what)
+    _launch_twin(xq, "smpq_trial_rows_conv_q", xq, x_absmax, n, h, w, cin, codes, int(lw), cout, kh, kw, stride, pad,
+                 col_scale, col_shift, int(L), residual_q, float(residual_range or 0.0), rows.channels, rows.n, yq,
+                 float(emit_range), overflow, save)
+    return rows
+
+
+def trial_rows_conv_restore(channels, yq, save):
+    """Put back the digit bytes trial_rows_conv saved for the same ``channels`` and planes."""
+    L, pixels, cout, rows = _trial_rows_conv_planes("trial_rows_conv_restore", yq, save, channels)
+    _launch_twin(yq, "smpq_trial_rows_conv_restore", rows.channels, rows.n, int(L), int(pixels), cout, yq, save)
+
+
 def image_quantize_s2d(x, x_absmax, limbs=None):
     """NCHW fp32 images (c <= 4, h, w >= 2) -> space-to-depth limb planes
     [limbs, n, ceil(h/2), ceil(w/2), 16] (channel (dy*2 + dx)*4 + c = pixel (2i+dy, 2j+dx), channel c;

@@ -207,13 +207,24 @@ def run_patched(trials, batches, hooks, table, flags, status, store=None):
     score(logits, y, row), invalidate(trial). The restore runs whatever happens; after an exception
     the conv's operand is also marked for repacking (invalidate), then the exception goes on.
     ``store`` (suffix.Store of the conv's block, or None): a batch it keeps runs through
-    hooks.resume(kept, block) instead, from the kept block input on."""
+    hooks.resume(kept, block) instead, from the kept block input on; when the conv is
+    the block's last and the store holds the rows route's tensors (``store.rows``),
+    through hooks.resume_rows(kept, block, channel): the patched channel alone is recomputed into
+    the kept input of the next block, which is put back before the operand is."""
     for i, tr in enumerate(trials):
         failed = False
+        rows = store is not None and store.rows is not None and store.rows is tr.conv
+        if rows:
+            store.row["rows_trials"] += 1
         try:
             hooks.patch(tr, status[i:i + 1])
             for kept, x, y in _walk(batches, store):
-                logits, ovf = hooks.forward(x) if kept is None else hooks.resume(kept, store.block)
+                if kept is None:
+                    logits, ovf = hooks.forward(x)
+                elif rows and kept.rows is not None:
+                    logits, ovf = hooks.resume_rows(kept, store.block, tr.channel)
+                else:
+                    logits, ovf = hooks.resume(kept, store.block)
                 _or_flags(flags[i], ovf)
                 hooks.score(logits, y, table[i])
         except BaseException:
@@ -392,16 +403,16 @@ def _select(net, lnums, channels):
     return cols
 
 
-def _suffix_plan(net, hooks, on, budget, base, base_kl=None):
+def _suffix_plan(net, hooks, on, budget, base, base_kl=None, rows=False):
     """The table's suffix.Plan (bound to ``hooks``), or None with the switch off."""
     if not on:
         return None
-    hooks.plan = _suffix.Plan(budget, base, base_kl, first=_suffix.first_block(net))
+    hooks.plan = _suffix.Plan(budget, base, base_kl, first=_suffix.first_block(net), rows=rows)
     return hooks.plan
 
 
 def delta_loss_table(net, batches, bits=(8, 6, 4), lnums=None, channels=None, progress=None, suffix=None,
-                     suffix_bytes=None):
+                     suffix_bytes=None, rows=None):
     """The delta-loss table of ``net`` on ``batches`` (a list of (x, y) device tensors, or a
     ResidentSet): for every selected conv (``lnums``, default all searched convs in
     assignments.conv_for_lnum's numbering), channel (``channels``: None = all, a sequence for every
@@ -421,8 +432,15 @@ def delta_loss_table(net, batches, bits=(8, 6, 4), lnums=None, channels=None, pr
     the trials of a deep enough block (smpq.suffix.MIN_SKIPPED) forward only the blocks from that one
     on, eagerly, from block inputs kept by one prefix pass per block under ``suffix_bytes`` (None:
     SMPQ_TRIAL_SUFFIX_GB, else unbounded); same statistics bit for bit, ``report()["suffix"]`` says
-    what was kept."""
+    what was kept.
+
+    ``rows`` (None: SMPQ_TRIAL_ROWS, off by default; honoured only with the suffix on): a trial of a
+    resumed block's LAST conv (conv3 of a Bottleneck, conv2 of a BasicBlock; not the net's last block)
+    computes only the patched output channel (ops.trial_rows_conv), in place into the kept input of
+    the next block, and resumes from that block; same statistics bit for bit, ``report()["suffix"]``
+    says per block whether the route was used or why not."""
     use_suffix, budget = _suffix.switch(suffix, suffix_bytes)
+    use_rows = _suffix.rows_switch(rows, use_suffix)
     bits = tuple(sorted({int(b) for b in bits}, reverse=True))
     if not bits or bits[-1] < 1 or bits[0] > 16:
         raise ValueError("smpq: bit-widths must be within 1..16")
@@ -451,7 +469,7 @@ def delta_loss_table(net, batches, bits=(8, 6, 4), lnums=None, channels=None, pr
     if any(bflags) or engine._signature(net) != cal.sig:
         raise RuntimeError("smpq: the baseline of the delta-loss sweep did not hold (overflow or changed weights)")
     base_loss = b[0] / b[3]
-    plan = _suffix_plan(net, hooks, use_suffix, budget, b)
+    plan = _suffix_plan(net, hooks, use_suffix, budget, b, rows=use_rows)
     mid = {k: stats.get(k, 0) for k in before}
     t1 = time.perf_counter()  # (the pass above ended in a host read)
 

@@ -15,6 +15,13 @@ and the producing conv's static range; ``amax`` is the shared range tensor of th
 up again at resume. The batch is cut into the slices ``engine._forward`` would give it, so every
 conv runs at a shape the replay route runs too, and the slices go one after another on the current
 stream. Block 0 (the stem's output) is supported like any other; the default cut never selects it.
+
+The rows route (``rows=True`` on delta_loss_table, SMPQ_TRIAL_ROWS=1): a trial of a
+block's LAST conv changes one channel of the next block's input, so the block's prefix pass
+(``fill_rows``) also keeps that input and what the last conv read (``RowsKept``), and the trial
+computes the patched channel alone into it (``rows_conv``, ops.trial_rows_conv), resumes from the
+next block and puts the bytes back (``rows_restore``). The one edit outside this module is
+engine.block_forward's optional ``keep`` tap.
 """
 import os
 import sys
@@ -65,6 +72,24 @@ def switch(suffix=None, suffix_bytes=None):
     return on, budget
 
 
+# SMPQ_TRIAL_ROWS=1: delta_loss_table's trials of a block's LAST conv recompute only the patched
+# output channel into the kept input of the next block and resume from there. Read at
+# import, off by default, honoured only with the suffix on, announced once on stderr at first use.
+TRIAL_ROWS = [os.environ.get("SMPQ_TRIAL_ROWS", "0") == "1"]
+_ROWS_ANNOUNCED = [False]
+
+
+def rows_switch(rows=None, suffix_on=True):
+    """Is the rows route on for a table? ``rows``: the table's argument (None: SMPQ_TRIAL_ROWS)."""
+    on = bool(suffix_on) and (TRIAL_ROWS[0] if rows is None else bool(rows))
+    if on and not _ROWS_ANNOUNCED[0]:
+        _ROWS_ANNOUNCED[0] = True
+        print("smpq: SMPQ_TRIAL_ROWS=1 -> delta-loss trials of a block's last conv recompute only the patched "
+              "output channel into the kept input of the next block and resume from there (smpq.suffix)",
+              file=sys.stderr)
+    return on
+
+
 def block_of(net, conv):
     """Forward-order index (prefix.block_names' numbering) of the block that owns the searched
     conv ``conv``; ValueError for a conv no block owns (the stem, a downsample)."""
@@ -104,11 +129,45 @@ def _producer(net, blocks, j):
 class Kept:
     """One batch's kept block input: per slice (start, end, limb planes, range), the batch's
     labels, its image count and the bytes of its planes."""
-    __slots__ = ("parts", "y", "n", "nbytes")
+    __slots__ = ("parts", "y", "n", "nbytes", "rows")
 
     def __init__(self, parts, n, y=None):
         self.parts, self.n, self.y = parts, n, y
         self.nbytes = sum(q.numel() * q.element_size() for _, _, q, _ in parts)
+        self.rows = None  # the rows route's extra tensors of this batch (RowsKept), or None
+
+
+def _nbytes(t):
+    return t.numel() * t.element_size()
+
+
+class RowsKept:
+    """What the rows route keeps of one batch of block j besides the block's input:
+    per slice the Acts fed to the block's last conv and added as its identity (engine.block_forward's
+    tap) and a save area for the digit bytes a trial replaces; ``next``: the Kept input of block
+    j + 1, the planes a trial writes one channel of. ``nbytes``: what this adds to the store (the
+    identity of a block without a downsample is the block input already kept)."""
+    __slots__ = ("taps", "saves", "next", "nbytes")
+
+    def __init__(self, taps, nxt, block_input):
+        self.taps, self.next = taps, nxt
+        self.saves = [torch.empty(ops.trial_rows_conv_save_bytes(q.shape[0], q[0, ..., 0].numel(), 1),
+                                  dtype=torch.int8, device=q.device) for _, _, q, _ in nxt.parts]
+        held = {p[2].data_ptr() for p in block_input.parts}
+        self.nbytes = nxt.nbytes + sum(_nbytes(s) for s in self.saves) + sum(
+            _nbytes(x.q) + (0 if ident.q.data_ptr() in held else _nbytes(ident.q)) for x, ident in taps)
+
+
+def rows_bytes(net, x, j):
+    """RowsKept.nbytes of batch ``x`` ([n, c, h, w]) at block ``j``, from the shapes alone (computed
+    before the fill): the last conv's input planes, the downsample's output planes where the block
+    has one, block j + 1's input planes and one channel's save area."""
+    blk = engine._blocks(net)[j]
+    last = blk.conv3 if hasattr(blk, "conv3") else blk.conv2
+    limbs, n, h, w, c = prefix.boundary_shape(net, j + 1, x.shape[0], x.shape[2], x.shape[3], ops.get_act_limbs())
+    nxt = prefix.boundary_bytes(limbs, c, h, w, n)
+    return (nxt + prefix.boundary_bytes(limbs, last.in_channels, h, w, n) + (nxt if blk.downsample is not None else 0)
+            + ops.trial_rows_conv_save_bytes(limbs, n * h * w, 1))
 
 
 def fill(net, x, cal, j):
@@ -136,6 +195,79 @@ def fill(net, x, cal, j):
     finally:
         ctx.n, ctx.lane = n, None
     return Kept(parts, n)
+
+
+def fill_rows(net, x, cal, j):
+    """fill(net, x, cal, j) whose one pass goes on through block ``j`` with engine.block_forward's tap:
+    (Kept or None, why). ``why`` is None when ``kept.rows`` holds the rows route's tensors, else the
+    reason it does not: "no_tap" (the last conv ran in a chain or fused-downsample launch, or not
+    from and to static limb planes) or "next_not_resumable" (block j + 1's input fails fill's rule).
+    The Kept itself is fill's, whatever ``why``."""
+    assert not torch.cuda.is_current_stream_capturing()
+    blocks = engine._blocks(net)
+    if not 0 <= j < len(blocks) - 1:
+        raise ValueError("smpq suffix: block %d has no next block to write into" % j)
+    n = x.shape[0]
+    ctx = engine.Ctx(n, x.device, ranges=cal.by_conv, cache=cal.tensors)
+    parts, taps, nparts, why = [], [], [], None
+    try:
+        for lane, (s0, s1) in enumerate(slices(n)):
+            ctx.n, ctx.lane = s1 - s0, lane
+            act, t1 = engine.stem_forward(net, x[s0:s1], ctx), None
+            for i in range(j):
+                act, t1 = engine.block_forward(blocks[i], act, ctx, last=False, t1=t1, nxt=blocks[i + 1])
+            if t1 is not None or act.q is None or act.rng is None or act.f32 is not None:
+                return None, None
+            parts.append((s0, s1, act.q, act.rng))
+            if why is None:
+                keep = {}
+                out, t1 = engine.block_forward(blocks[j], act, ctx, last=False, t1=None, nxt=blocks[j + 1], keep=keep)
+                if "x" not in keep:
+                    why = "no_tap"
+                elif t1 is not None or out.q is None or out.rng is None or out.f32 is not None:
+                    why = "next_not_resumable"
+                else:
+                    taps.append((keep["x"], keep["identity"]))
+                    nparts.append((s0, s1, out.q, out.rng))
+    finally:
+        ctx.n, ctx.lane = n, None
+    kept = Kept(parts, n)
+    if why is None:
+        kept.rows = RowsKept(taps, Kept(nparts, n), kept)
+    return kept, why
+
+
+def last_conv(net, j):
+    """(conv, bn) of block ``j``'s last conv: conv3 of a Bottleneck, conv2 of a BasicBlock."""
+    blk = engine._blocks(net)[j]
+    return (blk.conv3, blk.bn3) if hasattr(blk, "conv3") else (blk.conv2, blk.bn2)
+
+
+def rows_conv(net, kept, j, rows, flag, done):
+    """The rows route's write: the channel(s) ``rows`` (ops.TrialRows) of block ``j``'s last conv, from
+    its operand as it is now (patched or not), into every slice of ``kept.rows.next``
+    (ops.trial_rows_conv; the old bytes go to the slices' save areas, an overflow to ``flag`` int32
+    [1]). ``done`` (a list) grows by one per slice written, for rows_restore."""
+    conv, bn = last_conv(net, j)
+    plan = engine.conv_plan(conv, bn)
+    for (x, ident), save, (_, _, q, rng) in zip(kept.rows.taps, kept.rows.saves, kept.rows.next.parts):
+        ops.trial_rows_conv(x.q, x.amax, plan.codes, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0],
+                            conv.padding[0], plan.col_scale, plan.col_shift, rows, q, rng, flag, save,
+                            residual_q=ident.q, residual_range=ident.rng)
+        done.append(1)
+
+
+def rows_restore(kept, rows, done):
+    """Put back what rows_conv replaced in the first ``len(done)`` slices of ``kept.rows.next``."""
+    for _, save, (_, _, q, _) in zip(done, kept.rows.saves, kept.rows.next.parts):
+        ops.trial_rows_conv_restore(rows, q, save)
+
+
+def rows_geometry(conv):
+    """Is ``conv`` one of the two geometries ops.trial_rows_conv computes?"""
+    geo = (conv.kernel_size, conv.stride, conv.padding, conv.dilation, conv.groups)
+    return geo in (((1, 1), (1, 1), (0, 0), (1, 1), 1), ((3, 3), (1, 1), (1, 1), (1, 1), 1)) \
+        and conv.in_channels % 64 == 0 and conv.out_channels % 16 == 0 and ops.get_act_limbs() in (2, 3)
 
 
 def resume(net, kept, cal, j, check=True):
@@ -182,6 +314,9 @@ class Store:
     def __init__(self, budget=None):
         self.budget = None if budget is None else int(budget)
         self.block, self.entries, self.bytes = None, [], 0
+        # the rows route: the block's last conv while its trials may use the entries'
+        # RowsKept, else None; ``row``: the block's report row (rows trials are counted there)
+        self.rows, self.row = None, None
 
     def fits(self, nbytes):
         return self.budget is None or self.bytes + int(nbytes) <= self.budget
@@ -201,6 +336,22 @@ class Store:
         """Every batch becomes a full forward (the block turned out not to be resumable)."""
         self.entries = [None] * len(self.entries)
         self.bytes = 0
+
+    def drop_rows(self):
+        """Every kept batch goes back to the block's own input alone (no rows route for this block)."""
+        for e in self.entries:
+            if e is not None and e.rows is not None:
+                self.bytes -= e.rows.nbytes
+                e.rows = None
+        self.rows = None
+
+    @property
+    def rows_kept(self):
+        return sum(e is not None and e.rows is not None for e in self.entries)
+
+    @property
+    def rows_bytes(self):
+        return sum(e.rows.nbytes for e in self.entries if e is not None and e.rows is not None)
 
     @property
     def kept(self):
@@ -226,6 +377,7 @@ class Store:
 
     def release(self):
         self.block, self.entries, self.bytes = None, [], 0
+        self.rows, self.row = None, None
 
 
 class Plan:
@@ -235,11 +387,12 @@ class Plan:
     one per block visited; ``launches`` / ``resumed``: conv launches issued by, and number of,
     resumed forwards (self-checks included)."""
 
-    def __init__(self, budget, base, base_kl=None, first=0):
+    def __init__(self, budget, base, base_kl=None, first=0, rows=False):
         self.store = Store(budget)
         self.base, self.base_kl, self.first = list(base), None if base_kl is None else list(base_kl), first
         self.blocks, self.launches, self.resumed = [], 0, 0
         self.visited = None
+        self.rows = bool(rows)  # the rows route for the last convs of eligible blocks (DESIGN.md 5j)
 
     def report(self):
         return {"first_block": self.first, "blocks": [dict(b) for b in self.blocks],
@@ -252,7 +405,16 @@ def enter(plan, hooks, conv, batches, device, refs=None):
     beyond ``plan.first``, refilled by one eager prefix pass over ``batches``; then one unpatched
     pass through the suffix must reproduce ``plan.base`` (and ``plan.base_kl`` with ``refs``)
     bitwise, else RuntimeError. Hooks: block_of(conv), block_name(j), kept_bytes(x, j), fill(x, j)
-    -> Kept or None, resume(kept, j), forward(x), score / score_kl, sync()."""
+    -> Kept or None, resume(kept, j), forward(x), score / score_kl, sync().
+
+    With ``plan.rows`` the same pass also keeps, for every batch that fits with them,
+    what the rows route needs (``kept.rows``), ``store.rows`` becomes the block's last conv, and two
+    more checks run before any trial: the one-row kernel on the unpatched operand must leave the kept
+    planes as they are, and an unpatched resume from block j + 1 must reproduce the statistics too.
+    The block's report row says ``rows``: "used", or why not ("off", "below_cut", "last_block",
+    "geometry", "not_patchable", "no_tap", "next_not_resumable", "not_resumable", "budget"). More
+    hooks then: rows_block(j) -> None or why not, last_conv(j), rows_bytes(x, j), fill_rows(x, j) ->
+    (Kept or None, why), rows_check(store, j) -> bool."""
     j = hooks.block_of(conv)
     st = plan.store
     if plan.visited == j:
@@ -260,39 +422,94 @@ def enter(plan, hooks, conv, batches, device, refs=None):
     st.release()  # the block changes
     plan.visited = j
     row = {"block": j, "name": hooks.block_name(j), "used": j >= plan.first, "resumable": None, "kept": 0,
-           "full": None, "bytes": 0, "prefix_pass_s": 0.0, "self_check": None, "self_check_s": 0.0}
+           "full": None, "bytes": 0, "prefix_pass_s": 0.0, "self_check": None, "self_check_s": 0.0,
+           "rows": "off", "rows_kept": 0, "rows_trials": 0, "rows_bytes": 0, "rows_self_check": None,
+           "rows_self_check_s": 0.0}
     plan.blocks.append(row)
     if not row["used"]:
+        if plan.rows:
+            row["rows"] = "below_cut"
         return None
+    why = hooks.rows_block(j) if plan.rows else "off"  # None: the rows route is still possible
     hooks.sync()
     t0 = time.perf_counter()
     st.begin(j)
     resumable = True
     for x, y in batches:
         nb = hooks.kept_bytes(x, j)
+        extra = hooks.rows_bytes(x, j) if why is None else 0  # (all sizes before the fill)
         kept = None
-        if resumable and st.fits(nb):
+        if resumable and why is None and st.fits(nb + extra):
+            kept, why = hooks.fill_rows(x, j)
+            if why is not None:
+                st.drop_rows()
+        elif resumable and st.fits(nb):  # without the extra tensors: this batch is kept 5h's way
             kept = hooks.fill(x, j)
-            if kept is None:
-                resumable = False
-                st.drop_kept()
+        else:
+            nb = None  # not tried
+        if nb is not None and kept is None:
+            resumable = False
+            st.drop_kept()
+        more = 0
         if kept is not None:
             if kept.nbytes != nb:
                 raise RuntimeError("smpq suffix: block %d keeps %d bytes of a batch, %d expected" % (j, kept.nbytes, nb))
+            if kept.rows is not None:
+                more = kept.rows.nbytes
+                if more != extra:
+                    raise RuntimeError("smpq suffix: block %d keeps %d more bytes of a batch for the rows route, %d "
+                                       "expected" % (j, more, extra))
             kept.y = y
-        st.add(kept, nb)
+        st.add(kept, (nb or 0) + more)
     hooks.sync()
     row.update(resumable=resumable, kept=st.kept, full=len(st.entries) - st.kept, bytes=st.bytes,
                prefix_pass_s=time.perf_counter() - t0)
+    if plan.rows:
+        if why is None and not resumable:
+            why = "not_resumable"
+        elif why is None and not st.rows_kept:
+            why = "budget"
+        row.update(rows=why or "used", rows_kept=st.rows_kept, rows_bytes=st.rows_bytes)
     if not st.kept:
         return None
     # the self-check: no patch, through the suffix, against the table's unpatched replay pass
+    same, got = _unpatched(plan, st, hooks, batches, device, refs, j, False)
+    row["self_check"], row["self_check_s"] = same, time.perf_counter() - t0 - row["prefix_pass_s"]
+    if not same:
+        st.release()
+        raise RuntimeError("smpq suffix: block %s resumed without a patch does not reproduce the unpatched pass "
+                           "(statistics %r against %r)" % (row["name"], got, plan.base))
+    if st.rows_kept:
+        # the rows route's: the one-row kernel on the unpatched operand changes nothing, and the kept
+        # inputs of block j + 1 resume to the same statistics
+        t1 = time.perf_counter()
+        planes = hooks.rows_check(st, j)
+        same, got = _unpatched(plan, st, hooks, batches, device, refs, j, True)
+        row["rows_self_check"], row["rows_self_check_s"] = bool(planes and same), time.perf_counter() - t1
+        if not (planes and same):
+            st.release()
+            raise RuntimeError("smpq suffix: block %s fails the rows route's self-check (%s)" % (
+                row["name"], "the one-row conv of the unpatched operand changed the kept planes" if not planes else
+                "statistics %r against %r resumed from the next block" % (got, plan.base)))
+        st.rows, st.row = hooks.last_conv(j), row
+    return st
+
+
+def _unpatched(plan, st, hooks, batches, device, refs, j, rows):
+    """One unpatched pass over the store's batches: (does it reproduce the plan's base statistics
+    bitwise with zero flags?, the statistics). ``rows``: a batch with a RowsKept resumes from its
+    kept input of block j + 1 instead of block j's."""
     got = torch.zeros(4, dtype=torch.float64, device=device)
     kl = torch.zeros(2, dtype=torch.float64, device=device)
     flags = torch.zeros(2, dtype=torch.int32, device=device)
     walk = st.walk(batches)
     for (kept, x, y), ref in zip(walk, refs if refs is not None else _nones()):
-        logits, ovf = hooks.forward(x) if kept is None else hooks.resume(kept, j)
+        if kept is None:
+            logits, ovf = hooks.forward(x)
+        elif rows and kept.rows is not None:
+            logits, ovf = hooks.resume(kept.rows.next, j + 1)
+        else:
+            logits, ovf = hooks.resume(kept, j)
         torch.bitwise_or(flags, ovf, out=flags)
         if refs is None:
             hooks.score(logits, y, got)
@@ -301,12 +518,7 @@ def enter(plan, hooks, conv, batches, device, refs=None):
     for _ in walk:  # (run the generator to its end: its batch-count check)
         pass
     same = got.tolist() == plan.base and (refs is None or kl.tolist() == plan.base_kl) and not any(flags.tolist())
-    row["self_check"], row["self_check_s"] = same, time.perf_counter() - t0 - row["prefix_pass_s"]
-    if not same:
-        st.release()
-        raise RuntimeError("smpq suffix: block %s resumed without a patch does not reproduce the unpatched pass "
-                           "(statistics %r against %r)" % (row["name"], got.tolist(), plan.base))
-    return st
+    return same, got.tolist()
 
 
 def _nones():
@@ -347,3 +559,69 @@ class EngineHooks:
 
     def sync(self):
         torch.cuda.synchronize()
+
+    # ---- the rows route ----
+    def last_conv(self, j):
+        return last_conv(self.net, j)[0]
+
+    def rows_block(self, j):
+        """None when block ``j``'s last conv may go the rows route, else why not."""
+        from . import sensitivity  # (sensitivity imports this module)
+        if j >= len(engine._blocks(self.net)) - 1:
+            return "last_block"  # its output is fp32 for the average pool
+        conv, bn = last_conv(self.net, j)
+        if not rows_geometry(conv):
+            return "geometry"
+        return None if sensitivity.patchable(conv, bn) else "not_patchable"
+
+    def rows_bytes(self, x, j):
+        return rows_bytes(self.net, x, j)
+
+    def fill_rows(self, x, j):
+        return fill_rows(self.net, x, self.cal, j)
+
+    _row_list = None
+
+    def _one_row(self, j, channel, device):
+        """The uploaded one-entry list of a trial's channel (made once per trial, not per batch)."""
+        key = (j, int(channel), device)
+        if self._row_list is None or self._row_list[0] != key:
+            self._row_list = (key, ops.trial_rows_lists([int(channel)], 8, last_conv(self.net, j)[0].out_channels,
+                                                        device, "trial_rows_conv"))
+        return self._row_list[1]
+
+    def rows_check(self, st, j):
+        """The one-row conv of channel 0 from the UNPATCHED operand into every kept input of block
+        j + 1: the bytes it replaced must be the bytes it wrote (compared on the device, one host
+        read), and it must not flag an overflow."""
+        dev = next(e for e in st.entries if e is not None).parts[0][2].device
+        rows = self._one_row(j, 0, dev)
+        bad = torch.zeros(2, dtype=torch.int32, device=dev)
+        for e in st.entries:
+            if e is None or e.rows is None:
+                continue
+            done = []
+            try:
+                rows_conv(self.net, e, j, rows, bad[:1], done)
+                for save, (_, _, q, _) in zip(e.rows.saves, e.rows.next.parts):
+                    old = save[:q.shape[0] * q[0, ..., 0].numel()].view(q.shape[0], -1)
+                    bad[1:] |= (old != q.reshape(q.shape[0], -1, q.shape[-1])[:, :, 0]).any().to(torch.int32)
+            finally:
+                rows_restore(e, rows, done)
+        return not any(bad.tolist())
+
+    def resume_rows(self, kept, j, channel):
+        """A trial's forward of one batch on the rows route: channel ``channel`` of block ``j``'s last
+        conv from its patched operand into the kept input of block j + 1, the resumed forward from
+        there, the old bytes back (whatever happens): (logits, flags with the one-row conv's overflow
+        in word 0)."""
+        flag = torch.zeros(2, dtype=torch.int32, device=kept.parts[0][2].device)
+        rows = self._one_row(j, channel, flag.device)
+        done = []
+        try:
+            rows_conv(self.net, kept, j, rows, flag[:1], done)
+            logits, ovf = self.resume(kept.rows.next, j + 1)
+            torch.bitwise_or(flag, ovf, out=flag)
+        finally:
+            rows_restore(kept, rows, done)
+        return logits, flag
