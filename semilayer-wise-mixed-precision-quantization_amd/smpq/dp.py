@@ -127,3 +127,64 @@ def sharded_kldiv(n_out_local, out_local, world):
         ops.kl_rows(p, q, stats)
     s, n = all_reduce_stats(stats, world).tolist()
     return s / n
+
+
+# ---- sensitivity tables with their TRIALS sharded over the ranks ---------------------
+def _sharded_table(name, merge, net, batches, rank, world, group, kw):
+    """One rank of a sharded table: the table with shard=(rank, world), then the call's one
+    collective, an all_gather_object of (ok, payload) that every rank reaches exactly once whether
+    its sweep returned (payload: its table) or raised (payload: the exception as text)."""
+    from smpq import engine, sensitivity
+    from smpq.batches import ResidentSet
+    rank, world = sensitivity.check_shard((rank, world))
+    if engine.get_dp_group() is not None:
+        raise ValueError("smpq: %s runs outside dp.lockstep (its ranks share trials, not images)" % name)
+    if isinstance(batches, ResidentSet) and batches.shard is not None:
+        raise ValueError("smpq: %s needs the whole set on every rank, not a ResidentSet with shard %r "
+                         "(image shards would give another table)" % (name, batches.shard))
+    if world > 1 and (not dist.is_initialized() or dist.get_world_size(group) != world):
+        # (the group's size is the same for all its members: they all raise here, none waits)
+        raise ValueError("smpq: %s over %d ranks needs a process group of that size" % (name, world))
+    mine = (False, "rank %d left its sweep without a result" % rank)
+    try:
+        # a rank argument that is not the caller's rank in the group is that rank's own mistake: it
+        # goes through the gather like any failure of its sweep, so that no other rank waits for it
+        if world > 1 and dist.get_rank(group) != rank:
+            raise ValueError("called as rank %d, but it is rank %d of the group" % (rank, dist.get_rank(group)))
+        mine = (True, getattr(sensitivity, name)(net, batches, shard=(rank, world), **kw))
+    except Exception as e:  # noqa: BLE001 -- it travels to every rank as text
+        mine = (False, "%s: %s" % (type(e).__name__, e))
+    finally:
+        if world > 1:
+            parts = [None] * world
+            dist.all_gather_object(parts, mine, group=group)
+        else:  # nothing to gather: no process group is needed
+            parts = [mine]
+    failed = [(r, payload) for r, (ok, payload) in enumerate(parts) if not ok]
+    if failed:
+        raise RuntimeError("smpq: %s failed on %s" % (name, "; ".join("rank %d (%s)" % f for f in failed)))
+    return merge([payload for _, payload in parts])
+
+
+def sharded_delta_loss_table(net, batches, rank, world, group=None, **kw):
+    """sensitivity.delta_loss_table with its trials (not its images) shared among the ``world``
+    ranks of ``group`` (default: the whole world): this rank runs the columns
+    sensitivity.shard_owner gives it, on its own GPU, outside ``lockstep`` and with no collective
+    inside the sweep; then one all_gather_object of host objects (gloo is enough) and
+    sensitivity.merge_delta_loss. Every rank returns the same complete table, which is the
+    single-process table bit for bit. ``batches`` is the WHOLE set on every rank and ``kw`` are
+    delta_loss_table's arguments, the same on every rank. If any rank's sweep raised, every rank
+    raises RuntimeError naming the rank and its message; nothing is retried; a ``rank`` that is not
+    the caller's rank in the group counts as such a failure of that rank. ValueError (before any
+    work, on what is the same on every rank): inside ``lockstep``, a ResidentSet with a shard, no
+    process group of ``world`` ranks. ``world`` 1 needs no process group and gathers nothing."""
+    from smpq import sensitivity
+    return _sharded_table("delta_loss_table", sensitivity.merge_delta_loss, net, batches, rank, world, group, kw)
+
+
+def sharded_semilayer_table(net, batches, semilayers, rank, world, group=None, **kw):
+    """sharded_delta_loss_table for sensitivity.semilayer_table: semilayer i runs on rank
+    i % world, the parts are joined by sensitivity.merge_semilayers."""
+    from smpq import sensitivity
+    return _sharded_table("semilayer_table", sensitivity.merge_semilayers, net, batches, rank, world, group,
+                          dict(kw, semilayers=semilayers))

@@ -28,6 +28,7 @@ replayed trial's bit for bit.
 import csv
 import math
 import time
+import types
 
 import numpy as np
 import torch
@@ -131,7 +132,10 @@ class DeltaLossTable:
     float64 arrays (trial loss - base loss; nan for a constant channel), ``bits`` in the order of the
     file's rows (descending). ``base_loss``: the unquantized model's loss through the sweep's own
     replays (what patched trials are compared with); ``eval_loss``: the same model's loss from an
-    ordinary evaluation (what slow trials are compared with; it equals functions.evaluate_loss)."""
+    ordinary evaluation (what slow trials are compared with; it equals functions.evaluate_loss).
+    ``owned``: None, or on the table of a sharded call (``shard=(rank, world)``) a bool array per
+    column: the columns this rank computed; every other column is nan (so is a constant channel:
+    ``owned`` alone tells them apart). merge_delta_loss makes the complete table of the parts."""
 
     def __init__(self, arch, lnum, cnum, bits, delta, base_loss, eval_loss=None, report=None):
         self.arch = arch
@@ -144,18 +148,26 @@ class DeltaLossTable:
         # per bit [columns, 4]: a patched trial's softmax_xent statistics (loss sum, correct, rows,
         # batches); nan rows for slow trials and constant channels
         self.stats = {}
+        self.owned = None
         self._report = dict(report or {})
 
     def report(self):
         """Counters of the sweep: trials, patched, slow by reason, constant channels (listed),
         and the calibrations, graph captures and repacks seen by the baseline and by the trials;
-        ``suffix``: what the store kept per block (suffix.Plan.report(); {} with the switch off)."""
+        ``suffix``: what the store kept per block (suffix.Plan.report(); {} with the switch off).
+        A sharded call counts its own trials only and adds ``shard``: [rank, world]; a merged table
+        has the sums, ``world`` and ``ranks``: the parts' reports in rank order."""
         return dict(self._report)
 
 
 def write_csv(table, path):
     """The reference's layout (resnet18_main.py:61-84): row 0 lnum, row 1 the 1-based channel, then
-    one row per bit-width, descending; utf-8-sig, repr-exact floats, no empty trailing column."""
+    one row per bit-width, descending; utf-8-sig, repr-exact floats, no empty trailing column.
+    ValueError for the partial table of a sharded call (merge_delta_loss the parts first)."""
+    owned = getattr(table, "owned", None)
+    if owned is not None and not np.all(owned):
+        raise ValueError("smpq: write_csv of a partial table (%d of %d columns owned): merge the shards first"
+                         % (int(np.sum(owned)), len(owned)))
     with open(path, "w", encoding="utf-8-sig", newline="") as f:
         wr = csv.writer(f)
         wr.writerow([int(v) for v in table.lnum])
@@ -180,6 +192,46 @@ def read_csv(path, bits=None, arch=None):
     cnum = [int(v) - 1 for v in rows[1][:n]]
     delta = {int(b): [float(v) for v in rows[2 + i][:n]] for i, b in enumerate(bits)}
     return DeltaLossTable(arch, lnum, cnum, bits, delta, None)
+
+
+# ---- sharding a table's trials over ranks -------------------------------------------
+def check_shard(shard):
+    """``shard`` as (rank, world) ints, or None; ValueError unless world >= 1 and 0 <= rank < world."""
+    if shard is None:
+        return None
+    try:
+        rank, world = (int(v) for v in shard)
+    except (TypeError, ValueError):
+        raise ValueError("smpq: shard must be (rank, world), not %r" % (shard,)) from None
+    if world < 1 or not 0 <= rank < world:
+        raise ValueError("smpq: shard %r is not (rank, world) with world >= 1 and 0 <= rank < world" % (shard,))
+    return rank, world
+
+
+def shard_owner(world, lnum=None, count=None):
+    """The rank that owns each column of a sharded table, as an int64 array: the one assignment
+    both tables and their merges use. It depends on the selection alone, never on the model's
+    values, the data or a measured cost.
+
+    delta_loss_table: give ``lnum``, the lnum of every column in the table's order (what _select
+    gives; ``table.lnum``). The column at position i among the columns of ITS conv belongs to rank
+    i % world, with all its bit-widths: every rank visits every conv (and block) that has at least
+    ``world`` selected channels, and owns ceil or floor of each conv's share.
+    semilayer_table: give ``count``, the number of semilayers; semilayer i belongs to rank i % world."""
+    world = int(world)
+    if world < 1:
+        raise ValueError("smpq: world must be >= 1, not %d" % world)
+    if (lnum is None) == (count is None):
+        raise ValueError("smpq: shard_owner takes lnum (delta_loss_table) or count (semilayer_table)")
+    if lnum is None:
+        return np.arange(int(count), dtype=np.int64) % world
+    seen = {}
+    owner = np.empty(len(lnum), dtype=np.int64)
+    for col, ln in enumerate(lnum):
+        ln = int(ln)
+        owner[col] = seen.get(ln, 0) % world
+        seen[ln] = seen.get(ln, 0) + 1
+    return owner
 
 
 # ---- the sweep ---------------------------------------------------------------------------------
@@ -412,7 +464,7 @@ def _suffix_plan(net, hooks, on, budget, base, base_kl=None, rows=False):
 
 
 def delta_loss_table(net, batches, bits=(8, 6, 4), lnums=None, channels=None, progress=None, suffix=None,
-                     suffix_bytes=None, rows=None):
+                     suffix_bytes=None, rows=None, shard=None):
     """The delta-loss table of ``net`` on ``batches`` (a list of (x, y) device tensors, or a
     ResidentSet): for every selected conv (``lnums``, default all searched convs in
     assignments.conv_for_lnum's numbering), channel (``channels``: None = all, a sequence for every
@@ -438,7 +490,14 @@ def delta_loss_table(net, batches, bits=(8, 6, 4), lnums=None, channels=None, pr
     resumed block's LAST conv (conv3 of a Bottleneck, conv2 of a BasicBlock; not the net's last block)
     computes only the patched output channel (ops.trial_rows_conv), in place into the kept input of
     the next block, and resumes from that block; same statistics bit for bit, ``report()["suffix"]``
-    says per block whether the route was used or why not."""
+    says per block whether the route was used or why not.
+
+    ``shard=(rank, world)`` (None: every trial): this call runs only the trials of the columns
+    shard_owner gives ``rank`` and pays the whole baseline (and, per block it visits, the prefix pass
+    and self-checks); a conv of which it owns nothing is skipped. The table has every column, nan
+    outside ``table.owned``; merge_delta_loss of the ``world`` tables is the unsharded table bit for
+    bit. dp.sharded_delta_loss_table runs one rank of it and gathers."""
+    shard = check_shard(shard)
     use_suffix, budget = _suffix.switch(suffix, suffix_bytes)
     use_rows = _suffix.rows_switch(rows, use_suffix)
     bits = tuple(sorted({int(b) for b in bits}, reverse=True))
@@ -459,6 +518,7 @@ def delta_loss_table(net, batches, bits=(8, 6, 4), lnums=None, channels=None, pr
             raise ValueError("smpq: batches must be (x, y) pairs with x on the model's device, or a ResidentSet")
         batches = [(x, torch.as_tensor(y).to(p.device)) for x, y in batches]
     cols = _select(net, lnums, channels)
+    owned = None if shard is None else shard_owner(shard[1], lnum=[ln for ln, _, _ in cols]) == shard[0]
 
     before = {k: stats.get(k, 0) for k in ("calibrations", "graph_captures", "repack")}
     t0 = time.perf_counter()
@@ -488,6 +548,8 @@ def delta_loss_table(net, batches, bits=(8, 6, 4), lnums=None, channels=None, pr
         bn = bn_for(net, conv)
         trials = []
         for col, c in chans:
+            if owned is not None and not owned[col]:
+                continue
             for bit in bits:
                 if const_rows[ln][c]:  # the reference raises there (functions.py:40): nan, listed
                     counts["constant"].append((ln, c, bit))
@@ -514,16 +576,20 @@ def delta_loss_table(net, batches, bits=(8, 6, 4), lnums=None, channels=None, pr
     t2 = time.perf_counter()  # (so did the last conv's trials)
     if not counts["slow"] and (engine._signature(net) != cal.sig or engine.model_state(net).ranges is not cal):
         raise RuntimeError("smpq: the model changed while the delta-loss sweep ran")
-    report = {"trials": len(cols) * len(bits), "patched": counts["patched"], "overflowed": counts["overflowed"],
+    mine = len(cols) if owned is None else int(owned.sum())
+    report = {"trials": mine * len(bits), "patched": counts["patched"], "overflowed": counts["overflowed"],
               "slow": dict(counts["slow"]), "constant": list(counts["constant"]),
               "baseline": {k: mid[k] - before[k] for k in before},
               "during_trials": {k: after[k] - mid[k] for k in before},
               "baseline_s": t1 - t0, "trials_s": t2 - t1, "suffix": plan.report() if plan is not None else {}}
     for k in before:  # totals seen during the whole call
         report[{"graph_captures": "captures", "repack": "repacks"}.get(k, k)] = after[k] - before[k]
+    if shard is not None:
+        report["shard"] = list(shard)
     table = DeltaLossTable(arch_of(net), [ln for ln, _, _ in cols], [c for _, _, c in cols], bits, delta, base_loss,
                            eval_loss, report)
     table.stats = trial_stats
+    table.owned = owned
     return table
 
 
@@ -550,7 +616,8 @@ class SemilayerTable:
     (functions.KLdiv's sum / images against the reference outputs) as float64 arrays, nan for a
     semilayer with a constant channel; ``stats`` [., 4] and ``kl_stats`` [., 2] the raw statistics
     of a patched trial (nan rows for slow ones); ``slow`` marks the trials that ran through the
-    public API. ``base_loss`` / ``eval_loss`` as in DeltaLossTable."""
+    public API. ``base_loss`` / ``eval_loss`` as in DeltaLossTable; ``owned``: None, or the bool
+    array of the semilayers a sharded call ran (the others are nan; merge_semilayers)."""
 
     def __init__(self, arch, sems, base_loss, eval_loss, report=None):
         n = len(sems)
@@ -565,6 +632,7 @@ class SemilayerTable:
         self.stats = np.full((n, 4), np.nan, dtype=np.float64)
         self.kl_stats = np.full((n, 2), np.nan, dtype=np.float64)
         self.slow = np.zeros(n, dtype=bool)
+        self.owned = None
         self.base_loss, self.eval_loss = base_loss, eval_loss
         self._report = dict(report or {})
 
@@ -769,7 +837,8 @@ def _semilayers(net, semilayers):
     return sems
 
 
-def semilayer_table(net, batches, semilayers, reference_outputs=None, progress=None, suffix=None, suffix_bytes=None):
+def semilayer_table(net, batches, semilayers, reference_outputs=None, progress=None, suffix=None, suffix_bytes=None,
+                    shard=None):
     """The reference's semilayer sensitivity pass (functions._make_semilayers) on ``net`` as it is:
     for every ``(lnum, channels, bit)`` of ``semilayers`` (``bit``: one int or one per channel), the
     loss, top-1 accuracy and KL divergence against ``reference_outputs`` of the model with THOSE
@@ -782,7 +851,11 @@ def semilayer_table(net, batches, semilayers, reference_outputs=None, progress=N
     (ops.trial_rows_patch), replays the captured graphs, scores every batch eagerly and restores;
     it runs under the baseline's ranges, as delta_loss_table's trials do. Semilayers that are not
     patchable_rows and overflowed trials run afterwards through the public API on the model itself,
-    which is restored bitwise after each. ``suffix`` / ``suffix_bytes``: as in delta_loss_table."""
+    which is restored bitwise after each. ``suffix`` / ``suffix_bytes``: as in delta_loss_table.
+    ``shard=(rank, world)``: only the semilayers shard_owner gives ``rank`` (position i of
+    ``semilayers`` -> rank i % world) are run, after the whole baseline; ``table.owned`` marks them and
+    merge_semilayers joins the parts."""
+    shard = check_shard(shard)
     use_suffix, budget = _suffix.switch(suffix, suffix_bytes)
     if engine.get_range_mode() != "static":
         raise ValueError("smpq: semilayer_table needs the static range mode (engine.set_range_mode)")
@@ -799,6 +872,7 @@ def semilayer_table(net, batches, semilayers, reference_outputs=None, progress=N
             raise ValueError("smpq: batches must be (x, y) pairs with x on the model's device, or a ResidentSet")
         batches = [(x, torch.as_tensor(y).to(p.device)) for x, y in batches]
     sems = _semilayers(net, semilayers)
+    owned = None if shard is None else shard_owner(shard[1], count=len(sems)) == shard[0]
     if reference_outputs is not None:
         reference_outputs = [r.to(p.device) for r in reference_outputs]
 
@@ -827,9 +901,11 @@ def semilayer_table(net, batches, semilayers, reference_outputs=None, progress=N
 
     counts = {"patched": 0, "overflowed": 0, "slow": {}, "constant": [], "rows_patched": 0, "max_rows": 0}
     table = SemilayerTable(arch_of(net), sems, base_loss, eval_loss)
+    table.owned = owned
     by_conv = {}
     for sem in sems:
-        by_conv.setdefault(sem.lnum, []).append(sem)
+        if owned is None or owned[sem.index]:
+            by_conv.setdefault(sem.lnum, []).append(sem)
     groups = []
     with torch.no_grad():
         for ln, group in by_conv.items():
@@ -864,13 +940,142 @@ def semilayer_table(net, batches, semilayers, reference_outputs=None, progress=N
     t2 = time.perf_counter()
     if not counts["slow"] and (engine._signature(net) != cal.sig or engine.model_state(net).ranges is not cal):
         raise RuntimeError("smpq: the model changed while the semilayer sweep ran")
-    report = {"trials": len(sems), "patched": counts["patched"], "overflowed": counts["overflowed"],
-              "slow": dict(counts["slow"]), "constant": list(counts["constant"]),
+    report = {"trials": len(sems) if owned is None else int(owned.sum()), "patched": counts["patched"],
+              "overflowed": counts["overflowed"], "slow": dict(counts["slow"]), "constant": list(counts["constant"]),
               "rows_patched": counts["rows_patched"], "max_rows": counts["max_rows"],
               "baseline": {k: mid[k] - before[k] for k in before},
               "during_trials": {k: after[k] - mid[k] for k in before},
               "baseline_s": t1 - t0, "trials_s": t2 - t1, "suffix": plan.report() if plan is not None else {}}
     for k in before:
         report[{"graph_captures": "captures", "repack": "repacks"}.get(k, k)] = after[k] - before[k]
+    if shard is not None:
+        report["shard"] = list(shard)
     table._report = report
     return table
+
+
+# ---- merging the tables of a sharded call (host only) -------------------------------
+def _same_bits(a, b):
+    """Two losses equal as bits (float64), None only with None. No tolerance on purpose: every rank
+    computed the baseline from the same model and data, so a difference is a fault to be reported."""
+    if a is None or b is None:
+        return a is None and b is None
+    return np.float64(a).tobytes() == np.float64(b).tobytes()
+
+
+def _merge_owned(tables, n, what):
+    """The part that owns each of ``n`` columns (int array), after checking the parts' baselines and
+    that their ``owned`` masks are disjoint and cover every column (None counts as all true)."""
+    if not tables:
+        raise ValueError("smpq: nothing to merge")
+    first = tables[0]
+    for i, t in enumerate(tables):
+        if t.arch != first.arch:
+            raise ValueError("smpq: part %d is a table of %s, part 0 of %s" % (i, t.arch, first.arch))
+        shard = t.report().get("shard")
+        if shard is not None and list(shard) != [i, len(tables)]:
+            raise ValueError("smpq: part %d is shard %r of its call, not (%d, %d): the parts go in rank order, all of them"
+                             % (i, tuple(shard), i, len(tables)))
+        for name in ("base_loss", "eval_loss"):
+            if not _same_bits(getattr(t, name), getattr(first, name)):
+                raise ValueError("smpq: part %d has %s %r, part 0 has %r: the ranks did not see the same model and data"
+                                 % (i, name, getattr(t, name), getattr(first, name)))
+    part = np.full(n, -1, dtype=np.int64)
+    for i, t in enumerate(tables):
+        owned = np.ones(n, dtype=bool) if t.owned is None else np.asarray(t.owned, dtype=bool)
+        if owned.shape != (n,):
+            raise ValueError("smpq: part %d's owned mask has shape %r for %d %ss" % (i, owned.shape, n, what))
+        twice = np.flatnonzero(owned & (part >= 0))
+        if twice.size:
+            raise ValueError("smpq: %s %d is owned by part %d and part %d" % (what, twice[0], part[twice[0]], i))
+        part[owned] = i
+    missing = np.flatnonzero(part < 0)
+    if missing.size:
+        raise ValueError("smpq: %s %d is owned by no part" % (what, missing[0]))
+    return part
+
+
+def _merge_report(tables, extra=()):
+    reps = [t.report() for t in tables]
+    slow = {}
+    for r in reps:
+        for why, k in r.get("slow", {}).items():
+            slow[why] = slow.get(why, 0) + k
+    out = {k: sum(r.get(k, 0) for r in reps) for k in ("trials", "patched", "overflowed") + tuple(extra)}
+    out["slow"] = slow
+    out["constant"] = sorted(tuple(c) for r in reps for c in r.get("constant", ()))
+    out["world"] = len(tables)
+    out["baseline_s"] = max(r.get("baseline_s", 0.0) for r in reps)
+    out["trials_s"] = max(r.get("trials_s", 0.0) for r in reps)
+    out["ranks"] = reps
+    return out
+
+
+def merge_delta_loss(tables):
+    """The complete DeltaLossTable (``owned`` None) of the tables that the ranks of one sharded
+    delta_loss_table call returned, in rank order. Every column's deltas and trial statistics are
+    copied, as they are, from the part that owns it; nothing is averaged or recomputed, so the
+    result is the unsharded table bit for bit. ValueError, naming the first offending part or
+    column, unless arch, columns and bit-widths are the same, ``base_loss`` and ``eval_loss`` are
+    equal as bits in every part, and the ``owned`` masks are disjoint and cover every column.
+    report(): trials, patched, overflowed and slow summed, constant concatenated and sorted,
+    ``world``, ``ranks`` (the parts' reports in rank order), baseline_s / trials_s the maximum."""
+    tables = list(tables)
+    if not tables:
+        raise ValueError("smpq: nothing to merge")
+    first = tables[0]
+    for i, t in enumerate(tables):
+        if t.bits != first.bits:
+            raise ValueError("smpq: part %d has bit-widths %r, part 0 has %r" % (i, t.bits, first.bits))
+        if t.lnum.shape != first.lnum.shape:
+            raise ValueError("smpq: part %d has %d columns, part 0 has %d" % (i, len(t.lnum), len(first.lnum)))
+        differ = np.flatnonzero((t.lnum != first.lnum) | (t.cnum != first.cnum))
+        if differ.size:
+            raise ValueError("smpq: column %d is (lnum %d, channel %d) in part %d and (lnum %d, channel %d) in part 0"
+                             % (differ[0], t.lnum[differ[0]], t.cnum[differ[0]], i, first.lnum[differ[0]],
+                                first.cnum[differ[0]]))
+    n = len(first.lnum)
+    part = _merge_owned(tables, n, "column")
+    delta = {b: np.full(n, np.nan, dtype=np.float64) for b in first.bits}
+    stats_ = {b: np.full((n, 4), np.nan, dtype=np.float64) for b in first.bits}
+    for i, t in enumerate(tables):
+        mine = part == i
+        for b in first.bits:
+            delta[b][mine] = t.delta[b][mine]
+            if b in t.stats:
+                stats_[b][mine] = t.stats[b][mine]
+    out = DeltaLossTable(first.arch, first.lnum, first.cnum, first.bits, delta, first.base_loss, first.eval_loss,
+                         _merge_report(tables))
+    out.stats = stats_
+    return out
+
+
+def merge_semilayers(tables):
+    """merge_delta_loss for the SemilayerTables of one sharded semilayer_table call: ``loss``,
+    ``acc``, ``kl``, ``stats``, ``kl_stats`` and ``slow`` of every semilayer come from the part that
+    owns it. The parts must list the same semilayers (lnum, channels, bits). report() also sums
+    ``rows_patched`` and takes the maximum of ``max_rows``."""
+    tables = list(tables)
+    if not tables:
+        raise ValueError("smpq: nothing to merge")
+    first = tables[0]
+    for i, t in enumerate(tables):
+        if len(t.channels) != len(first.channels):
+            raise ValueError("smpq: part %d has %d semilayers, part 0 has %d" % (i, len(t.channels), len(first.channels)))
+        for j in range(len(first.channels)):
+            if int(t.lnum[j]) != int(first.lnum[j]) or t.channels[j] != first.channels[j] or t.bits[j] != first.bits[j]:
+                raise ValueError("smpq: semilayer %d of part %d is not part 0's" % (j, i))
+    n = len(first.channels)
+    part = _merge_owned(tables, n, "semilayer")
+    # (SemilayerTable reads lnum, channels, bits and param of each entry, nothing else)
+    sems = [types.SimpleNamespace(lnum=int(first.lnum[j]), channels=first.channels[j], bits=first.bits[j],
+                                  param=float(first.param[j])) for j in range(n)]
+    out = SemilayerTable(first.arch, sems, first.base_loss, first.eval_loss)
+    for i, t in enumerate(tables):
+        mine = part == i
+        for name in ("loss", "acc", "kl", "stats", "kl_stats", "slow"):
+            getattr(out, name)[mine] = getattr(t, name)[mine]
+    rep = _merge_report(tables, extra=("rows_patched",))
+    rep["max_rows"] = max(r.get("max_rows", 0) for r in rep["ranks"])
+    out._report = rep
+    return out
