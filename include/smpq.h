@@ -350,11 +350,20 @@ int smpq_conv2d_tile_config(int cfg, int* bm, int* bn, int* threads);
  *                              SMPQ_E_INVALID. A persistent workgroup keeps its slab's weight limbs
  *                              in registers and walks pixel tiles; BM = pixels per tile, BN = the
  *                              slab. Configurations follow the halo ones.
+ *   SMPQ_TILE_RESIDENT1X1_W    (ABI 7, appended) the same four geometries for the 1x1 convs of a
+ *                              model under search: 1x1 / stride 1 / pad 0 convs with 3 activation
+ *                              limbs and 3 weight limbs (24-bit fixed point), cin 64 .. 512 (per
+ *                              configuration: smpq_conv2d_tile_supported), cout a multiple of the
+ *                              slab, no weight offsets, ReLU on, static-range limb-plane output
+ *                              (yq set; y, y_absmax, residual NULL), with or without residual_q —
+ *                              other calls return SMPQ_E_INVALID. Configurations follow the
+ *                              SMPQ_TILE_RESIDENT1X1 ones; tile_cfg = -1 never picks one.
  * (negative: error code). Values 0 and 1 were the register-staged family (ABI <= 3, removed). */
 #define SMPQ_TILE_LDS_DMA 2
 #define SMPQ_TILE_LDS_DMA_K128 3
 #define SMPQ_TILE_HALO3X3 4
 #define SMPQ_TILE_RESIDENT1X1 5
+#define SMPQ_TILE_RESIDENT1X1_W 6
 int smpq_conv2d_tile_kind(int cfg);
 
 /* 1 if tile configuration cfg can run a conv of this shape and these limb counts (the rules the

@@ -107,6 +107,11 @@ void resident_cfg_info(int cfg, int* bm, int* bn, int* threads);
 bool resident_supported(int cfg, int cin, int cout, int kh, int kw, int limbs, int wlimbs);
 int launch_resident(int cfg, int limbs, int wlimbs, const ConvArgs& a, hipStream_t s);
 bool glds_is_resident(int cfg);
+// the same geometries with 3 weight limbs + ReLU (SMPQ_TILE_RESIDENT1X1_W); their configs come last
+int resident_w_num_cfgs();
+bool resident_w_supported(int cfg, int cin, int cout, int kh, int kw, int limbs, int wlimbs);
+int launch_resident_w(int cfg, int limbs, int wlimbs, const ConvArgs& a, hipStream_t s);
+bool glds_is_resident_w(int cfg);
 // the Bottleneck tail chains: conv3 (+ fused downsample) (-> next conv1) (smpq_conv2d_chain_fwd)
 bool resident_pair_supported(int cin, int cout1, int cout2, int limbs);
 bool resident_chain_ds_supported(int cin, int cout1, int ds_cin, int ds_stride, int limbs);

@@ -17,19 +17,24 @@ SMPQ_GLDS_FAMILY(3, 3)
 
 constexpr int kNumGlds = sizeof(kGlds) / sizeof(kGlds[0]);
 
-int glds_num_cfgs() { return kNumGlds + halo_num_cfgs() + resident_num_cfgs(); }
+int glds_num_cfgs() { return kNumGlds + halo_num_cfgs() + resident_num_cfgs() + resident_w_num_cfgs(); }
 
-// numbering: LDS-DMA configs, then halo configs, then the weight-stationary 1x1 configs
+// numbering: LDS-DMA configs, then halo configs, then the weight-stationary 1x1 configs, then those
+// with 3 weight limbs + ReLU
 static int res_base() { return kNumGlds + halo_num_cfgs(); }
+static int resw_base() { return res_base() + resident_num_cfgs(); }
 
 bool glds_is_halo(int cfg) { return cfg >= kNumGlds && cfg < res_base(); }
 
-bool glds_is_resident(int cfg) { return cfg >= res_base(); }
+bool glds_is_resident(int cfg) { return cfg >= res_base() && cfg < resw_base(); }
+
+bool glds_is_resident_w(int cfg) { return cfg >= resw_base(); }
 
 int glds_cfg_bk(int cfg) { return cfg >= kNumGlds ? 64 : kGlds[cfg].bk; }
 
 // Same rules as launch_one / launch_glds (accumulator budget, K-step width, LDS per CU).
 bool glds_supported(int cfg, int cin, int cout, int kh, int kw, int limbs, int wlimbs) {
+  if (cfg >= resw_base()) return resident_w_supported(cfg - resw_base(), cin, cout, kh, kw, limbs, wlimbs);
   if (cfg >= res_base()) return resident_supported(cfg - res_base(), cin, cout, kh, kw, limbs, wlimbs);
   if (cfg >= kNumGlds) return halo_supported(cfg - kNumGlds, cin, cout, kh, kw, limbs, wlimbs);
   const GldsCfg& c = kGlds[cfg];
@@ -68,6 +73,7 @@ int glds_default_cfg(const ConvArgs& a, int limbs, int wlimbs) {
 }
 
 void glds_cfg_info(int cfg, int* bm, int* bn, int* threads) {
+  if (cfg >= resw_base()) return resident_cfg_info(cfg - resw_base(), bm, bn, threads);
   if (cfg >= res_base()) return resident_cfg_info(cfg - res_base(), bm, bn, threads);
   if (cfg >= kNumGlds) return halo_cfg_info(cfg - kNumGlds, bm, bn, threads);
   const GldsCfg& c = kGlds[cfg];
@@ -93,6 +99,7 @@ int launch_glds(int cfg, int limbs, int wlimbs, const ConvArgs& a, hipStream_t s
   if ((!a.s2d && a.cin % kKStep != 0) || a.cout % 16 != 0 || !glds_planes_ok(a, limbs, wlimbs))
     return fail(SMPQ_E_INVALID,
                 "smpq_conv2d_fwd: LDS-DMA tile configs need cin % 64 == 0, cout % 16 == 0 and planes < 2 GiB");
+  if (cfg >= resw_base()) return launch_resident_w(cfg - resw_base(), limbs, wlimbs, a, s);
   if (cfg >= res_base()) return launch_resident(cfg - res_base(), limbs, wlimbs, a, s);
   if (cfg >= kNumGlds) return launch_halo(cfg - kNumGlds, limbs, wlimbs, a, s);
   if (a.s2d) {

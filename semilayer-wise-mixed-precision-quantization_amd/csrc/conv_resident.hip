@@ -53,12 +53,15 @@ namespace {
 struct ResCfg {
   int cw, wp;   // 16-channel fragments per wave (slab = 64 cw channels), 16-pixel fragments per tile
   int kc_mask;  // bit k: K = 64 k supported (chunks of 64 bytes per activation row)
+  // the same, of the geometry's SMPQ_TILE_RESIDENT1X1_W configuration (3 weight limbs + ReLU: the
+  // convs of a model under search): kc_mask cut by res_fits(3, k, cw)
+  int w_mask;
 };
 constexpr ResCfg kRes[] = {
-    {4, 2, 1 << 1},                                // 0: slab 256, 32 px, K 64 (the 64 -> 256 downsample)
-    {4, 1, (1 << 1) | (1 << 2) | (1 << 4)},        // 1: slab 256, 16 px, K 64..256 (the expansions)
-    {1, 1, 0x10116},                               // 2: slab 64, 16 px, K 64..1024 (strided ds, reductions)
-    {2, 1, 0x10116},                               // 3: slab 128, 16 px, K 64..1024
+    {4, 2, 1 << 1, 1 << 1},                          // 0: slab 256, 32 px, K 64 (the 64 -> 256 downsample)
+    {4, 1, (1 << 1) | (1 << 2) | (1 << 4), 0x6},     // 1: slab 256, 16 px, K 64..256 (the expansions)
+    {1, 1, 0x10116, 0x116},                          // 2: slab 64, 16 px, K 64..1024 (strided ds, reductions)
+    {2, 1, 0x10116, 0x16},                           // 3: slab 128, 16 px, K 64..1024
     // (slab 64 x 32 px at K 256 / 512 measured 1.1-2.1x slower than 16 px: one workgroup per CU)
 };
 // the weight fragments a wave holds: at most 32 (128 VGPRs)
@@ -599,10 +602,11 @@ int device_cus_res() {
   return cus;
 }
 
-template <int L, int LW, int CFG, int KC, bool RELU, bool RES, bool OFF>
+// W: a SMPQ_TILE_RESIDENT1X1_W configuration (the geometry's w_mask instead of its kc_mask)
+template <int L, int LW, int CFG, int KC, bool RELU, bool RES, bool OFF, bool W = false>
 int launch_res_one(const ConvArgs& a, hipStream_t s) {
   constexpr int CW = kRes[CFG].cw, WP = kRes[CFG].wp;
-  if constexpr (!((kRes[CFG].kc_mask >> KC) & 1) || !res_fits(LW, KC, CW)) {
+  if constexpr (!(((W ? kRes[CFG].w_mask : kRes[CFG].kc_mask) >> KC) & 1) || !res_fits(LW, KC, CW)) {
     return fail(SMPQ_E_INVALID, "smpq_conv2d_fwd: resident tile: cin not built for this configuration");
   } else {
   using S = ResShape<L, LW, KC, CW, WP, RES, 0, 0, OFF>;
@@ -629,26 +633,26 @@ int launch_res_one(const ConvArgs& a, hipStream_t s) {
   }
 }
 
-template <int L, int LW, int CFG, bool RELU, bool RES, bool OFF>
+template <int L, int LW, int CFG, bool RELU, bool RES, bool OFF, bool W = false>
 int launch_res_kc(int kc, const ConvArgs& a, hipStream_t s) {
   switch (kc) {  // only the K sizes of the configuration's mask are instantiated
-    case 1: return launch_res_one<L, LW, CFG, 1, RELU, RES, OFF>(a, s);
-    case 2: return launch_res_one<L, LW, CFG, 2, RELU, RES, OFF>(a, s);
-    case 4: return launch_res_one<L, LW, CFG, 4, RELU, RES, OFF>(a, s);
-    case 8: return launch_res_one<L, LW, CFG, 8, RELU, RES, OFF>(a, s);
-    case 16: return launch_res_one<L, LW, CFG, 16, RELU, RES, OFF>(a, s);
+    case 1: return launch_res_one<L, LW, CFG, 1, RELU, RES, OFF, W>(a, s);
+    case 2: return launch_res_one<L, LW, CFG, 2, RELU, RES, OFF, W>(a, s);
+    case 4: return launch_res_one<L, LW, CFG, 4, RELU, RES, OFF, W>(a, s);
+    case 8: return launch_res_one<L, LW, CFG, 8, RELU, RES, OFF, W>(a, s);
+    case 16: return launch_res_one<L, LW, CFG, 16, RELU, RES, OFF, W>(a, s);
     default: return fail(SMPQ_E_INVALID, "smpq_conv2d_fwd: resident tile: cin not built");
   }
 }
 
-template <int L, int LW, bool RELU, bool RES, bool OFF = false>
+template <int L, int LW, bool RELU, bool RES, bool OFF = false, bool W = false>
 int launch_res_l(int cfg, const ConvArgs& a, hipStream_t s) {
   const int kc = a.cin / 64;
   switch (cfg) {
-    case 0: return launch_res_kc<L, LW, 0, RELU, RES, OFF>(kc, a, s);
-    case 1: return launch_res_kc<L, LW, 1, RELU, RES, OFF>(kc, a, s);
-    case 2: return launch_res_kc<L, LW, 2, RELU, RES, OFF>(kc, a, s);
-    default: return launch_res_kc<L, LW, 3, RELU, RES, OFF>(kc, a, s);
+    case 0: return launch_res_kc<L, LW, 0, RELU, RES, OFF, W>(kc, a, s);
+    case 1: return launch_res_kc<L, LW, 1, RELU, RES, OFF, W>(kc, a, s);
+    case 2: return launch_res_kc<L, LW, 2, RELU, RES, OFF, W>(kc, a, s);
+    default: return launch_res_kc<L, LW, 3, RELU, RES, OFF, W>(kc, a, s);
   }
 }
 
@@ -687,8 +691,10 @@ void resident_cfg_info(int cfg, int* bm, int* bn, int* threads) {
   *threads = kResThreads;
 }
 
-// What tile_supported can see; the launcher also needs pad 0, no weight offsets and the
-// static-range limb-plane epilogue without a residual (yq set; y, y_absmax, residual, residual_q NULL).
+// What tile_supported can see: the shape rule. launch_resident also needs pad 0 and the static-range
+// limb-plane epilogue (yq set; y, y_absmax and the fp32 residual NULL), and runs these variants: 3
+// weight limbs without ReLU, residual_q or weight offsets (the downsamples); 1 weight limb with ReLU,
+// optionally with residual_q, both with or without weight offsets; 1 weight limb with neither.
 bool resident_supported(int cfg, int cin, int cout, int kh, int kw, int limbs, int wlimbs) {
   if (cfg < 0 || cfg >= kNumRes || kh != 1 || kw != 1 || limbs != 3 || !(wlimbs == 1 || wlimbs == 3)) return false;
   const ResCfg& c = kRes[cfg];
@@ -720,6 +726,33 @@ int launch_resident(int cfg, int limbs, int wlimbs, const ConvArgs& a, hipStream
     return launch_res_l<3, 1, true, true>(cfg, a, s);
   }
   return a.relu ? launch_res_l<3, 1, true, false>(cfg, a, s) : launch_res_l<3, 1, false, false>(cfg, a, s);
+}
+
+// SMPQ_TILE_RESIDENT1X1_W: the same four geometries for the 1x1 convs of a model under search, whose
+// operand is 24-bit fixed point because the conv still has a free channel (3 weight limbs, 6 MFMA
+// passes) and whose epilogue has ReLU: a Bottleneck's conv1 (ReLU) and conv3 (ReLU + limb-plane
+// identity). The same kernel template at LW = 3, RELU, with and without RES; K per geometry: w_mask.
+int resident_w_num_cfgs() { return kNumRes; }
+
+// What tile_supported can see; launch_resident_w also needs stride 1, pad 0, ReLU, no weight
+// offsets and the static-range limb-plane epilogue (yq set; y, y_absmax and the fp32 residual NULL).
+bool resident_w_supported(int cfg, int cin, int cout, int kh, int kw, int limbs, int wlimbs) {
+  if (cfg < 0 || cfg >= kNumRes || kh != 1 || kw != 1 || limbs != 3 || wlimbs != 3) return false;
+  const ResCfg& c = kRes[cfg];
+  return cin % 64 == 0 && cin / 64 < 31 && ((c.w_mask >> (cin / 64)) & 1) && cout % (64 * c.cw) == 0 &&
+         res_fits(3, cin / 64, c.cw);
+}
+
+int launch_resident_w(int cfg, int limbs, int wlimbs, const ConvArgs& a, hipStream_t s) {
+  if (!resident_w_supported(cfg, a.cin, a.cout, a.kh, a.kw, limbs, wlimbs) || a.pad != 0 || a.stride != 1 || a.s2d)
+    return fail(SMPQ_E_INVALID, "smpq_conv2d_fwd: resident 3-weight-limb tiles take 1x1 / stride 1 / pad 0 convs with "
+                                "3 activation limbs, 3 weight limbs and the tile's cin (64 .. 512) and slab of couts");
+  // (a.w_off: an offset array is refused as such; has_offset is only ever set with one weight limb)
+  if (!a.yq || a.y || a.residual || a.y_absmax || !a.relu || a.has_offset || a.w_off)
+    return fail(SMPQ_E_INVALID, "smpq_conv2d_fwd: resident 3-weight-limb tiles run the static-range limb-plane "
+                                "epilogue with ReLU (with a limb-plane residual or none), without weight offsets");
+  return a.res_q ? launch_res_l<3, 3, true, true, false, true>(cfg, a, s)
+                 : launch_res_l<3, 3, true, false, false, true>(cfg, a, s);
 }
 
 // Bottleneck conv3 (+ identity, ReLU) chained with the next block's conv1 (ReLU; cout2 = 0: none)

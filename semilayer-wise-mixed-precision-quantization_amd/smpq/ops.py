@@ -669,12 +669,14 @@ def tile_configs():
 
 
 TILE_LDS_DMA, TILE_LDS_DMA_K128, TILE_HALO3X3, TILE_RESIDENT1X1 = 2, 3, 4, 5  # include/smpq.h SMPQ_TILE_*
+TILE_RESIDENT1X1_W = 6
 _KINDS = {}
 
 
 def tile_kind(cfg):
     """Kernel family of a tile config (TILE_LDS_DMA / TILE_LDS_DMA_K128: 64- or 128-wide K steps;
-    TILE_HALO3X3: the halo-patch 3x3 kernel, static-range limb-plane output only)."""
+    TILE_HALO3X3: the halo-patch 3x3 kernel, static-range limb-plane output only;
+    TILE_RESIDENT1X1 / TILE_RESIDENT1X1_W: the weight-stationary 1x1 tiles)."""
     tile_configs()
     return _KINDS[cfg]
 
@@ -922,6 +924,10 @@ AUTOTUNE = [os.environ.get("SMPQ_AUTOTUNE", "1") != "0"]
 TUNE_REPS = [int(os.environ.get("SMPQ_TUNE_REPS", "10"))]
 # diagnostics (A/B of tile families on one box): tile configs the autotuner never tries
 TILES_EXCLUDED = {int(c) for c in os.environ.get("SMPQ_TILES_EXCLUDE", "").split(",") if c.strip()}
+# SMPQ_RESIDENT_W=1: the TILE_RESIDENT1X1_W configurations are candidates for the 1x1 convs they run (3
+# weight limbs + ReLU: a model under search); 0: the candidates are those without the kind. On by the
+# rule and the measurement in DESIGN §5l (the pristine ResNet-50 forward: 7.80 against 8.64 ms per batch).
+RESIDENT_W = [os.environ.get("SMPQ_RESIDENT_W", "1") != "0"]
 # tools/tune_tiles.py --concurrent: time each candidate as TUNE_CONCURRENT copies launched together on
 # their own streams (the timed forward runs its batch slices concurrently, and a tile's isolated time
 # does not predict how it shares the GPU with the other slice's kernels); TUNE_LOG keeps every
@@ -1051,23 +1057,51 @@ def tuned_conv2d_q(xq, x_absmax, codes, offset, kh, kw, stride, pad, col_scale, 
 
     def run(c):
         conv2d_q(*args, tile_cfg=c, **kwargs)
+    gates = _conv_tile_gates(kh, kw, stride, pad, wlimbs, offset, residual, relu, y_absmax, out, emit_range,
+                             want_f32, residual_q)
+    variant = _conv_tile_variant(gates)
+    # this process's cache first: the candidate list (one smpq_conv2d_tile_supported call per tile
+    # configuration) is built only for a key's first call
+    cfg = _TUNED.get(key if variant is None else (key, variant))
+    if cfg is None:
+        cfg = _choose_tile(key, run, _conv_tile_candidates(limbs, wlimbs, cout, cin, kh, gates), variant=variant)
+    return conv2d_q(*args, tile_cfg=-1 if cfg is None else cfg, **kwargs)
+
+
+def _conv_tile_gates(kh, kw, stride, pad, wlimbs, offset, residual, relu, y_absmax, out, emit_range, want_f32,
+                     residual_q):
+    """(halo_ok, res_ok, resw_ok): which lean-epilogue tile kinds may run this tuned_conv2d_q call.
+    The key does not carry relu / y_absmax / offset, so other calls of a key never see them."""
+    lean = emit_range is not None and not want_f32 and residual is None and y_absmax is None and out is None
     # the halo tiles run only the static-range limb-plane epilogue with ReLU, optionally with a
-    # limb-plane residual (stride 1 / pad 1 for now): the key does not carry relu / y_absmax, so
-    # other calls of a key never see them
-    halo_ok = bool(relu and emit_range is not None and not want_f32 and residual is None
-                   and y_absmax is None and out is None and kh == 3 and kw == 3 and stride == 1 and pad == 1)
+    # limb-plane residual (stride 1 / pad 1 for now)
+    halo_ok = bool(lean and relu and kh == 3 and kw == 3 and stride == 1 and pad == 1)
     # the weight-stationary 1x1 tiles: the static-range limb-plane epilogue, built for the
     # downsamples (3 weight limbs, no ReLU or residual) and for exact-code convs with ReLU + a
     # limb-plane residual, ReLU only (both also with weight offsets), or neither
     # (smpq_conv2d_tile_supported checks the shape)
-    res_ok = bool(emit_range is not None and not want_f32 and residual is None and y_absmax is None
-                  and out is None and kh == 1 and kw == 1 and pad == 0
+    res_ok = bool(lean and kh == 1 and kw == 1 and pad == 0
                   and (offset is None or (wlimbs == 1 and relu))
                   and (not (relu or residual_q is not None) if wlimbs == 3 else (relu or residual_q is None)))
-    cands = [c for c in tile_configs() if _tile_fits(c, limbs, wlimbs, cout, cin, kh)
-             and (halo_ok or tile_kind(c) != TILE_HALO3X3) and (res_ok or tile_kind(c) != TILE_RESIDENT1X1)]
-    cfg = _choose_tile(key, run, cands, variant=None if (halo_ok or res_ok) else "nohalo")
-    return conv2d_q(*args, tile_cfg=-1 if cfg is None else cfg, **kwargs)
+    # the same with 3 weight limbs + ReLU (with or without a limb-plane residual, stride 1): the
+    # 1x1 convs of a model under search, whose operand is fixed point while a channel is free
+    resw_ok = bool(RESIDENT_W[0] and lean and relu and offset is None and kh == 1 and kw == 1 and pad == 0
+                   and stride == 1 and wlimbs == 3)
+    return halo_ok, res_ok, resw_ok
+
+
+def _conv_tile_variant(gates):
+    """The cache variant of a call: separates calls of one key whose candidate sets differ."""
+    halo_ok, res_ok, resw_ok = gates
+    return "resw" if resw_ok else (None if (halo_ok or res_ok) else "nohalo")
+
+
+def _conv_tile_candidates(limbs, wlimbs, cout, cin, kh, gates):
+    """The tile configurations tuned_conv2d_q may choose from for a call with these gates."""
+    halo_ok, res_ok, resw_ok = gates
+    return [c for c in tile_configs() if _tile_fits(c, limbs, wlimbs, cout, cin, kh)
+            and (halo_ok or tile_kind(c) != TILE_HALO3X3) and (res_ok or tile_kind(c) != TILE_RESIDENT1X1)
+            and (resw_ok or tile_kind(c) != TILE_RESIDENT1X1_W)]
 
 
 def conv2d_nhwc(x, x_absmax, codes, offset, kh, kw, stride, pad, col_scale, col_shift,
