@@ -39,13 +39,11 @@ import time
 
 import torch
 
-from . import assignments, engine, ops, prefix, sensitivity
+from . import assignments, engine, prefix, sensitivity, trials
 from . import suffix as _suffix
-from .batches import ResidentSet
-from .qconv import stats
 from .quant import channel_wise_quantizationperchan, check_pending
 
-_COUNTERS = ("calibrations", "graph_captures", "repack")
+_COUNTERS = trials.COUNTERS
 
 
 class Result:
@@ -69,24 +67,17 @@ class Result:
             self.route, self.resumed_from)
 
 
-class EngineHooks(sensitivity._RowsHooks):
-    """What a Session asks of the engine (tests inject a fake): sensitivity's rows hooks, plus the
-    exact8 patch, the route, the commit and the session's views of the model."""
+class EngineHooks(trials.EngineHooks):
+    """What a Session asks of the engine (tests inject a fake): the trials' hooks, plus the route, the
+    commit and the session's views of the model."""
 
     def __init__(self, net, batches):
-        super().__init__(net, None, batches, None)
+        super().__init__(net, batches)
         self.device = next(net.parameters()).device
 
     # -- the state -----------------------------------------------------------------------------
     def semilayer(self, lnum, channels, bit):
         return sensitivity._semilayers(self.net, [(lnum, channels, bit)])[0]
-
-    def rebind(self):
-        """After an ordinary evaluation: bind the ranges it installed, forget the last conv and the
-        state's snapshot. Returns the ranges object."""
-        self.cal = engine.model_state(self.net).ranges
-        self._conv = self._state = None
-        return self.cal
 
     def held(self):
         """Is the model what the ranges were installed for?"""
@@ -96,38 +87,36 @@ class EngineHooks(sensitivity._RowsHooks):
         return engine._signature(self.net)
 
     def counters(self):
-        return tuple(stats.get(k, 0) for k in _COUNTERS)
+        return trials.counters()
 
     def ordinary_eval(self):
-        return sensitivity.ordinary_eval(self.net, self.batches)
+        return trials.ordinary_eval(self.net, self.batches)
 
     def kl_of(self, reference, outs):
-        return sensitivity.kl_of(reference, outs)
+        return trials.kl_of(reference, outs)
 
     def unpatched_pass(self):
-        return sensitivity._unpatched_pass_probs(self, self.batches, self.device)
+        return trials.unpatched_pass(self, self.batches, self.device, True)
 
     def kl_stats(self, refs, probs):
-        st = torch.zeros(2, dtype=torch.float64, device=self.device)
-        for ref, p in zip(refs, probs):
-            ops.kl_rows(ref, p, st)
-        return st.tolist()
+        return trials.kl_stats(refs, probs)
 
     def constant_rows(self, conv):
-        with torch.no_grad():
-            w2d = conv.weight.detach().reshape(conv.out_channels, -1)
-            return (w2d.amax(1) == w2d.amin(1)).tolist()
+        return trials.constant_rows(conv)
 
     def route(self, sem):
-        bn = sensitivity.bn_for(self.net, sem.conv)
-        if sensitivity.patchable_rows(sem.conv, bn, sem.channels):
+        bn = trials.bn_for(self.net, sem.conv)
+        if trials.patchable_rows(sem.conv, bn, sem.channels):
             return "patched"
-        if sensitivity.patchable_rows_x8(sem.conv, bn, sem.channels, sem.bits):
+        if trials.patchable_rows_x8(sem.conv, bn, sem.channels, sem.bits):
             return "patched_x8"
         return None
 
     def zeros(self, n, dtype):
         return torch.zeros(n, dtype=dtype, device=self.device)
+
+    def prepare_one(self, sem, route):
+        self.prepare([sem], "rows_x8" if route == "patched_x8" else "rows")
 
     # -- boundaries ----------------------------------------------------------------------------
     def block_index(self, name):
@@ -135,31 +124,6 @@ class EngineHooks(sensitivity._RowsHooks):
 
     def boundary_conv(self, j):
         return assignments.blocks_of(self.net)[j].conv1
-
-    # -- the patches ---------------------------------------------------------------------------
-    def prepare_one(self, sem, route):
-        self._bind(sem.conv)
-        lw, cout, K = self._plan.codes.shape
-        sem.rows = ops.trial_rows_lists(sem.channels, sem.bits, cout, self._plan.codes.device,
-                                        max_bits=8 if route == "patched_x8" else 16)
-        need = ops.trial_rows_save_bytes(lw, K, len(sem.channels))
-        if self._rows_save is None or self._rows_save.numel() < need or self._rows_save.device != self._plan.codes.device:
-            self._rows_save = torch.empty(need, dtype=torch.int8, device=self._plan.codes.device)
-        self._route = route
-
-    def patch(self, sem, status):
-        if self._route != "patched_x8":
-            return super().patch(sem, status)
-        self._bind(sem.conv)
-        self.new_trial()
-        ops.trial_rows_patch_x8(sem.conv.weight.detach(), sem.rows, None, self._a, self._plan.codes, self._plan.offset,
-                                self._wscale, self._plan.col_scale, self._rows_save, status, km=self._km)
-
-    def restore(self, sem):
-        if self._route != "patched_x8":
-            return super().restore(sem)
-        ops.trial_rows_restore_x8(sem.rows, self._plan.codes, self._plan.offset, self._wscale, self._plan.col_scale,
-                                  self._rows_save, km=self._km)
 
     # -- the commit -----------------------------------------------------------------------------
     def commit(self, sem):
@@ -184,20 +148,7 @@ class Session:
 
     def __init__(self, net, batches, reference_outputs=None, boundaries=None, boundary_bytes=None, hooks=None):
         if hooks is None:
-            if engine.get_range_mode() != "static":
-                raise ValueError("smpq: search.Session needs the static range mode (engine.set_range_mode)")
-            if engine.get_dp_group() is not None:
-                raise ValueError("smpq: search.Session runs on one GPU (no data-parallel group)")
-            p = next(net.parameters())
-            if not p.is_cuda or net.training or not getattr(net, "fused", True):
-                raise ValueError("smpq: search.Session needs an eval-mode smpq ResNet on the GPU")
-            if isinstance(batches, ResidentSet):
-                batches.bind(p.device)
-            else:
-                batches = list(batches)
-                if not batches or any(not (torch.is_tensor(x) and x.device == p.device) for x, _ in batches):
-                    raise ValueError("smpq: batches must be (x, y) pairs with x on the model's device, or a ResidentSet")
-                batches = [(x, torch.as_tensor(y).to(p.device)) for x, y in batches]
+            p, batches = trials.setup("search.Session", net, batches)
             if reference_outputs is not None:
                 reference_outputs = [r.to(p.device) for r in reference_outputs]
             hooks = EngineHooks(net, batches)
@@ -336,27 +287,18 @@ class Session:
         table, kl = hooks.zeros(4, torch.float64), hooks.zeros(2, torch.float64)
         flags, status = hooks.zeros(2, torch.int32), hooks.zeros(n, torch.int32)
         before = hooks.counters()
-        failed = False
         hooks.plan = plan
         try:
-            hooks.patch(sem, status)
-            walk = ((None, x, y) for x, y in self.batches) if plan is None else plan.store.walk(self.batches)
             with torch.no_grad():
-                for (kept, x, y), ref in zip(walk, self.reference):
-                    logits, ovf = hooks.forward(x) if kept is None else hooks.resume(kept, j)
-                    torch.bitwise_or(flags, ovf, out=flags)
-                    hooks.score_kl(logits, y, ref, table, kl)
+                trials.guarded_trial(hooks, sem, status, self.batches, None if plan is None else plan.store,
+                                     self.reference, table, kl, flags)
         except BaseException:
-            failed = True
+            self._release()
+            self._last = None
+            self._pending = self._pending or "exception"
             raise
         finally:
             hooks.plan = None
-            hooks.restore(sem)
-            if failed:
-                hooks.invalidate(sem)
-                self._release()
-                self._last = None
-                self._pending = self._pending or "exception"
         got = torch.cat([table, kl, flags.to(torch.float64), status.to(torch.float64)]).tolist()  # the one host read
         after = hooks.counters()
         for k, a, c in zip(_COUNTERS, before, after):

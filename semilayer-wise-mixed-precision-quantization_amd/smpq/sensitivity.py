@@ -28,96 +28,15 @@ replayed trial's bit for bit.
 import csv
 import math
 import time
-import types
 
 import numpy as np
 import torch
 
-from . import assignments, checkpoint, engine, ops
+from . import assignments, engine
 from . import suffix as _suffix  # (the tables have a ``suffix`` argument)
-from .batches import ResidentSet
-from .qconv import QConv2d, stats
-from .quant import channel_wise_quantizationperchan, check_pending
-
-
-def bn_for(net, conv):
-    """The BatchNorm the engine folds onto ``conv`` (convN -> bnN of its block), or None."""
-    for b in assignments.blocks_of(net):
-        for i in (1, 2, 3):
-            if getattr(b, "conv%d" % i, None) is conv:
-                return getattr(b, "bn%d" % i, None)
-    return None
-
-
-def patchable(conv, bn, channel=None):
-    """Can a trial of ``conv`` (folded with ``bn``) patch its packed operand in place? True when
-      * the conv has a ConvPlan whose codes are [LW, cout, K] with LW >= 2 and no offsets (kinds
-        'fixed' and 'exact16': every row coded independently of the others);
-      * another channel stays unquantized whichever channel is tried (``channel``: besides that
-        one), so the normal path would pack the quantized model with the same LW: a trial that
-        completes a conv would turn it 'exact8' there;
-      * the K-major copy on the codes is there exactly when ops.KMAJOR is on;
-      * K is within the patch kernel's row limit."""
-    free = _patchable_operand(conv, bn)
-    if free is None:
-        return False
-    others = int(free.sum()) - (1 if channel is None or free[int(channel)] else 0)
-    return others >= 1
-
-
-def _patchable_operand(conv, bn):
-    """patchable's conditions on the operand alone: the conv's free (unquantized) channel mask, or
-    None when its packed operand cannot be patched in place whatever the channels."""
-    if not isinstance(conv, QConv2d):
-        return None
-    plan = engine.conv_plan(conv, bn)
-    if plan is None or plan.codes.dim() != 3 or plan.codes.shape[0] < 2 or plan.offset is not None:
-        return None
-    if (getattr(plan.codes, "_smpq_km", None) is not None) != bool(ops.KMAJOR[0]):
-        return None
-    if plan.codes.shape[2] % 64 != 0 or plan.codes.shape[2] > ops.TRIAL_MAX_K:
-        return None
-    return np.asarray(conv._bits_host <= 0)
-
-
-def patchable_rows(conv, bn, channels):
-    """patchable for a semilayer trial: patchable's conditions on the operand, and at least one
-    channel OUTSIDE ``channels`` is unquantized (a semilayer that completes a conv would be packed
-    'exact8' on the normal path, with another LW)."""
-    free = _patchable_operand(conv, bn)
-    if free is None:
-        return False
-    free = free.copy()
-    free[[int(c) for c in channels]] = False
-    return bool(free.any())
-
-
-def patchable_rows_x8(conv, bn, channels, bits):
-    """Can a trial that RE-quantizes ``channels`` of a fully quantized ``conv`` at ``bits`` (one
-    int or one per channel) patch its 'exact8' operand in place (ops.trial_rows_patch_x8)? True when
-      * the conv has a ConvPlan whose codes are [1, cout, K] of kind 'exact8';
-      * the K-major copy on the codes is there exactly when ops.KMAJOR is on;
-      * K is a multiple of 64 within the patch kernel's row limit;
-      * every channel of the conv is quantized, so that it stays fully quantized whatever the
-        channels and the normal path would again pack one int8 plane;
-      * every bit-width is at most 8 (a wider row cannot be exact8).
-    Whether a ROW can then be coded (on the grid, within 256 levels, with an offset only where the
-    operand has offsets) is the kernel's answer, in its status words. codes, their K-major copy,
-    offset, wscale and the folded col_scale are all an exact8 operand is: the resident 1x1 tiles, the
-    halo 3x3 tiles and the chained conv3 / conv1 launches read these same tensors."""
-    if not isinstance(conv, QConv2d):
-        return False
-    plan = engine.conv_plan(conv, bn)
-    if plan is None or getattr(plan, "kind", None) != "exact8" or plan.codes.dim() != 3 or plan.codes.shape[0] != 1:
-        return False
-    if (getattr(plan.codes, "_smpq_km", None) is not None) != bool(ops.KMAJOR[0]):
-        return False
-    if plan.codes.shape[2] % 64 != 0 or plan.codes.shape[2] > ops.TRIAL_MAX_K:
-        return False
-    if not conv.fully_quantized():
-        return False
-    bits = [bits] if isinstance(bits, (int, np.integer)) else list(bits)
-    return len([int(c) for c in channels]) > 0 and all(1 <= int(b) <= 8 for b in bits)
+from .trials import (COUNTERS, EngineHooks, Semilayer, Trial, bn_for, constant_rows, counters, guarded_trial, kl_stats,
+                     ordinary_eval, ordinary_loss, patchable, patchable_rows, setup, unpatched_pass)
+from .trials import kl_of, patchable_rows_x8  # noqa: F401 (part of this module's face, with the names above)
 
 
 def arch_of(net):
@@ -235,99 +154,73 @@ def shard_owner(world, lnum=None, count=None):
 
 
 # ---- the sweep ---------------------------------------------------------------------------------
-class Trial:
-    __slots__ = ("col", "lnum", "conv", "channel", "bit")
-
-    def __init__(self, col, lnum, conv, channel, bit):
-        self.col, self.lnum, self.conv, self.channel, self.bit = col, lnum, conv, channel, bit
-
-
-def _or_flags(dst, ovf):
-    torch.bitwise_or(dst, ovf, out=dst)
-
-
-def _walk(batches, store):
-    """(kept input or None, x, y) per batch: the store's walk, or every batch in full without one."""
-    return ((None, x, y) for x, y in batches) if store is None else store.walk(batches)
-
-
-def run_patched(trials, batches, hooks, table, flags, status, store=None):
-    """The patched trials of ONE conv, without a host sync: for trial i patch, forward every batch
-    into ``table[i]`` (float64 [4] softmax_xent statistics), OR the replays' flags into ``flags[i]``
-    (int32 [2]: overflow, stale content), restore. ``status[i]`` is the patch's constant-channel
-    word. ``hooks``: patch(trial, status_word), restore(trial), forward(x) -> (logits, flag tensor),
-    score(logits, y, row), invalidate(trial). The restore runs whatever happens; after an exception
-    the conv's operand is also marked for repacking (invalidate), then the exception goes on.
-    ``store`` (suffix.Store of the conv's block, or None): a batch it keeps runs through
-    hooks.resume(kept, block) instead, from the kept block input on; when the conv is
-    the block's last and the store holds the rows route's tensors (``store.rows``),
-    through hooks.resume_rows(kept, block, channel): the patched channel alone is recomputed into
-    the kept input of the next block, which is put back before the operand is."""
+def run_patched(trials, batches, hooks, table, flags, status, store=None, refs=None, kl=None):
+    """The patched trials of ONE conv, without a host sync: trials.guarded_trial for trial i with
+    ``table[i]``, ``flags[i]``, its status words ``status[i]`` and, with ``refs``, ``kl[i]``."""
     for i, tr in enumerate(trials):
-        failed = False
-        rows = store is not None and store.rows is not None and store.rows is tr.conv
-        if rows:
-            store.row["rows_trials"] += 1
-        try:
-            hooks.patch(tr, status[i:i + 1])
-            for kept, x, y in _walk(batches, store):
-                if kept is None:
-                    logits, ovf = hooks.forward(x)
-                elif rows and kept.rows is not None:
-                    logits, ovf = hooks.resume_rows(kept, store.block, tr.channel)
-                else:
-                    logits, ovf = hooks.resume(kept, store.block)
-                _or_flags(flags[i], ovf)
-                hooks.score(logits, y, table[i])
-        except BaseException:
-            failed = True
-            raise
-        finally:
-            hooks.restore(tr)
-            if failed:
-                hooks.invalidate(tr)
+        guarded_trial(hooks, tr, status[i], batches, store, refs, table[i], None if kl is None else kl[i], flags[i])
 
 
-def _by_block(groups, hooks):
-    """``groups`` in block order (stable), so that a table fills the store once per block."""
-    return sorted(groups, key=lambda g: hooks.block_of(g[1][0].conv))
+def _figures(row, kl_row=None):
+    """What a table reports of a patched trial's raw statistics: (loss,), with a KL row (loss, top-1, KL)."""
+    if kl_row is None:
+        return (row[0] / row[3],)
+    return row[0] / row[3], row[1] / row[2], kl_row[0] / kl_row[1]
 
 
-def sweep(groups, batches, hooks, device, out, counts, progress=None, plan=None):
-    """Every trial of ``groups`` ([(patchable?, [Trial, ...]), ...], one group per conv): the
-    patched ones conv by conv (one host sync per conv), then the slow ones (convs that are not
-    patchable, overflowed trials) through ``hooks.slow(trial) -> loss``. ``out(trial, loss, slow, row)``
-    receives every result (``row``: a patched trial's four statistics, else None); ``counts`` the bookkeeping.
-    ``plan`` (suffix.Plan or None): the groups are visited in block order and the patched trials of
-    a block run from its kept inputs (suffix.enter); the store is released when the block changes,
-    after the last patched trial and on any exception."""
+def sweep(groups, batches, hooks, device, out, counts, progress=None, plan=None, refs=None):
+    """Every trial of ``groups`` ([(patchable?, [Trial or Semilayer, ...]), ...], one group per conv):
+    the patched ones conv by conv (one host sync per conv), then the slow ones (convs that are not
+    patchable, overflowed trials) through ``hooks.slow(trial)``. ``refs``: None for the delta-loss
+    table (a trial's figures are (loss,), hooks.slow gives the loss), the reference softmax per batch
+    for the semilayer table (figures (loss, top-1, KL), every batch scored against its reference,
+    hooks.slow gives (acc, loss, kl)). ``out(trial, *figures, slow, row)``, with ``refs``
+    ``out(trial, *figures, slow, row, kl_row)``, receives every result (``row`` / ``kl_row``: a patched
+    trial's raw statistics, else None); a constant channel makes its
+    trial's figures nan and is listed in ``counts``, the bookkeeping (``rows_patched`` and ``max_rows``
+    are kept when it has them). ``plan`` (suffix.Plan or None): the groups are visited in block order
+    and the patched trials of a block run from its kept inputs (suffix.enter, whose self-check also
+    compares the KL statistics with ``refs``); the store is released when the block changes, after
+    the last patched trial and on any exception."""
+    what = "delta-loss" if refs is None else "semilayer"
+    blank = (math.nan,) * (1 if refs is None else 3)
+    none = (None,) if refs is None else (None, None)  # a trial without raw statistics
     slow = []
     done = 0
-    if plan is not None:
-        groups = _by_block(groups, hooks)
+    if plan is not None:  # block order (stable), so that the store is filled once per block
+        groups = sorted(groups, key=lambda g: hooks.block_of(g[1][0].conv))
     try:
         for fast, trials in groups:
             if not fast:
                 slow += [(tr, "not_patchable") for tr in trials]
                 continue
-            store = None if plan is None else _suffix.enter(plan, hooks, trials[0].conv, batches, device)
+            store = None if plan is None else _suffix.enter(plan, hooks, trials[0].conv, batches, device, refs)
+            widths = [len(tr.channels) for tr in trials]
             table = torch.zeros(len(trials), 4, dtype=torch.float64, device=device)
+            kl = None if refs is None else torch.zeros(len(trials), 2, dtype=torch.float64, device=device)
             flags = torch.zeros(len(trials), 2, dtype=torch.int32, device=device)
-            status = torch.zeros(len(trials), dtype=torch.int32, device=device)
-            run_patched(trials, batches, hooks, table, flags, status, store)
-            rows, fl, st = table.tolist(), flags.tolist(), status.tolist()  # the conv's one host sync
-            for tr, row, (ovf, stale), const in zip(trials, rows, fl, st):
+            words = torch.zeros(sum(widths), dtype=torch.int32, device=device)
+            run_patched(trials, batches, hooks, table, flags, torch.split(words, widths), store, refs, kl)
+            rows, kls = table.tolist(), [None] * len(trials) if kl is None else kl.tolist()
+            fl, st = flags.tolist(), words.tolist()  # the conv's one host sync
+            at = 0
+            for tr, n, row, klrow, (ovf, stale) in zip(trials, widths, rows, kls, fl):
+                const = [(tr.lnum, c, b) for c, b, word in zip(tr.channels, tr.bits, st[at:at + n]) if word]
+                at += n
                 if stale:
-                    raise RuntimeError("smpq: the model's weights changed while the delta-loss sweep ran")
-                if const:
-                    counts["constant"].append((tr.lnum, tr.channel, tr.bit))
-                    out(tr, math.nan, False, None)
+                    raise RuntimeError("smpq: the model's weights changed while the %s sweep ran" % what)
+                if const:  # the whole trial nan, its constant channels listed
+                    counts["constant"] += const
+                    out(tr, *blank, False, *none)
                 elif ovf:
                     counts["overflowed"] += 1
                     slow.append((tr, "overflow"))
                 else:
                     counts["patched"] += 1
-                    out(tr, row[0] / row[3], False, row)
+                    if "rows_patched" in counts:
+                        counts["rows_patched"] += n
+                        counts["max_rows"] = max(counts["max_rows"], n)
+                    out(tr, *_figures(row, klrow), False, *((row,) if kl is None else (row, klrow)))
             done += len(trials)
             if progress is not None:
                 progress(done, counts)
@@ -337,101 +230,20 @@ def sweep(groups, batches, hooks, device, out, counts, progress=None, plan=None)
     for tr, why in slow:
         counts["slow"][why] = counts["slow"].get(why, 0) + 1
         try:
-            loss = hooks.slow(tr)
+            got = hooks.slow(tr)
+            figures = (got,) if refs is None else (got[1], got[0], got[2])
         except ZeroDivisionError:  # the reference raises on a constant channel (functions.py:40)
-            counts["constant"].append((tr.lnum, tr.channel, tr.bit))
-            loss = math.nan
-        out(tr, loss, True, None)
+            counts["constant"] += [(tr.lnum, c, b) for c, b in zip(tr.channels, tr.bits)]
+            figures = blank
+        out(tr, *figures, True, *none)
         done += 1
         if progress is not None:
             progress(done, counts)
 
 
-class _EngineHooks(_suffix.EngineHooks):
-    """The sweep's hooks on the real engine: ``cal`` the StaticRanges installed by the baseline.
-    (suffix.EngineHooks adds what a table with a suffix.Plan calls: block_of, fill, resume.)"""
-
-    def __init__(self, net, cal, batches):
-        self.net, self.cal, self.batches = net, cal, batches
-        self._conv = None
-        self._state = None
-
-    def _bind(self, conv):
-        if self._conv is not conv:
-            bn = bn_for(self.net, conv)
-            plan = engine.conv_plan(conv, bn)
-            with torch.no_grad():
-                a = engine._bn_fold(bn)[0].contiguous() if bn is not None else torch.ones_like(plan.col_scale)
-                wscale = conv.packed()[3]
-                lw, _, K = plan.codes.shape
-                self._save = torch.empty(ops.trial_save_bytes(lw, K), dtype=torch.int8, device=plan.codes.device)
-            self._conv, self._plan, self._a, self._wscale = conv, plan, a, wscale
-            self._km = getattr(plan.codes, "_smpq_km", None)
-
-    def patch(self, tr, status):
-        self._bind(tr.conv)
-        self.new_trial()
-        ops.trial_row_patch(tr.conv.weight.detach(), tr.channel, tr.bit, self._a, self._plan.codes, self._wscale,
-                            self._plan.col_scale, self._save, status, km=self._km)
-
-    def restore(self, tr):
-        ops.trial_row_restore(tr.channel, self._plan.codes, self._wscale, self._plan.col_scale, self._save, km=self._km)
-
-    def invalidate(self, tr):
-        tr.conv._content_gen += 1
-
-    def forward(self, x):
-        if engine.USE_GRAPH[0]:
-            return engine._graph_forward(self.net, x, self.cal)
-        return engine._static_eager(self.net, x, self.cal)
-
-    def score(self, logits, y, row):
-        ops.softmax_xent(logits.float().contiguous(), y, row, want_probs=False)
-
-    def slow(self, tr):
-        """One trial through the public API on the model itself: quantize the channel, evaluate as
-        functions.evaluate_loss does, put weight and metadata back bitwise."""
-        if self._state is None:
-            self._state = checkpoint.snapshot(self.net)
-        try:
-            channel_wise_quantizationperchan(tr.conv.weight.data, tr.bit, tr.channel)
-            check_pending()
-            return ordinary_loss(self.net, self.batches)
-        finally:
-            try:
-                check_pending()
-            except ZeroDivisionError:
-                pass
-            checkpoint.restore_(self.net, self._state)
-
-
-def ordinary_loss(net, batches):
-    """functions.evaluate_loss on device batches: a fresh calibration on the first batch, the mean
-    over batches of the batch-mean cross entropy from float64 statistics (one host sync)."""
-    acc = None
-    engine.new_evaluation(net)
-    with torch.no_grad():
-        for x, y in batches:
-            out = net(x).float().contiguous()
-            if acc is None:
-                acc = torch.zeros(4, dtype=torch.float64, device=out.device)
-            ops.softmax_xent(out, y, acc, want_probs=False)
-    loss_sum, _, _, count = acc.tolist()
-    return loss_sum / count
-
-
-def _unpatched_pass(hooks, batches, device):
-    """Every batch through the trials' own forward with no patch: (statistics, flags) on the host.
-    (A function of its own: a replay hands out its graph's flag tensor, which lives in the graph
-    pool; nothing here outlives the call, so a later release of the graphs frees the pool whole.)"""
-    base = torch.zeros(4, dtype=torch.float64, device=device)
-    flags = torch.zeros(2, dtype=torch.int32, device=device)
-    with torch.no_grad():
-        for x, y in batches:
-            logits, ovf = hooks.forward(x)
-            _or_flags(flags, ovf)
-            hooks.score(logits, y, base)
-    return base.tolist(), flags.tolist()
+def sweep_rows(groups, batches, refs, hooks, device, out, counts, progress=None, plan=None):
+    """sweep with ``refs`` (the semilayer table's call, in its earlier argument order)."""
+    sweep(groups, batches, hooks, device, out, counts, progress, plan, refs)
 
 
 def _select(net, lnums, channels):
@@ -455,12 +267,56 @@ def _select(net, lnums, channels):
     return cols
 
 
-def _suffix_plan(net, hooks, on, budget, base, base_kl=None, rows=False):
-    """The table's suffix.Plan (bound to ``hooks``), or None with the switch off."""
-    if not on:
-        return None
-    hooks.plan = _suffix.Plan(budget, base, base_kl, first=_suffix.first_block(net), rows=rows)
-    return hooks.plan
+class _Run:
+    """What both tables do around their sweep: the baseline before it, the report after it."""
+
+    def __init__(self, what, net, batches, want_probs):
+        """The baseline of the ``what`` sweep: one ordinary evaluation installs the static ranges
+        (``eval_loss``; with ``want_probs`` its softmax outputs ``eval_outs``), the hooks are bound to
+        them, one unpatched pass of the trials' own forward captures every graph (``base``: its
+        statistics, ``base_loss``; ``base_probs``) and must hold."""
+        self.what, self.net = what, net
+        self.before, self.t0 = counters(), time.perf_counter()
+        if want_probs:
+            _, self.eval_loss, self.eval_outs = ordinary_eval(net, batches)
+        else:
+            self.eval_loss, self.eval_outs = ordinary_loss(net, batches), None
+        self.hooks = EngineHooks(net, batches)
+        self.cal = self.hooks.rebind()
+        device = next(net.parameters()).device
+        self.base, flags, self.base_probs = unpatched_pass(self.hooks, batches, device, want_probs)
+        if any(flags) or engine._signature(net) != self.cal.sig:
+            raise RuntimeError("smpq: the baseline of the %s sweep did not hold (overflow or changed weights)" % what)
+        self.base_loss = self.base[0] / self.base[3]
+        self.plan = None
+
+    def suffix_plan(self, budget, base_kl=None, rows=False):
+        """Visit the convs in block order through a suffix.Plan bound to the hooks."""
+        self.plan = _suffix.Plan(budget, self.base, base_kl, first=_suffix.first_block(self.net), rows=rows)
+        self.hooks.plan = self.plan
+
+    def start(self):
+        """The baseline ends here (the unpatched pass ended in a host read), the trials begin."""
+        self.mid, self.t1 = counters(), time.perf_counter()
+        return {"patched": 0, "overflowed": 0, "slow": {}, "constant": []}
+
+    def report(self, trials, counts, shard):
+        """The trials ended (the last conv's in a host read): the model must be what the baseline left
+        unless a slow trial ran; the table's report()."""
+        after, t2 = counters(), time.perf_counter()
+        if not counts["slow"] and (engine._signature(self.net) != self.cal.sig
+                                   or engine.model_state(self.net).ranges is not self.cal):
+            raise RuntimeError("smpq: the model changed while the %s sweep ran" % self.what)
+        rep = dict(counts, slow=dict(counts["slow"]), constant=list(counts["constant"]))
+        rep.update(trials=trials, baseline=dict(zip(COUNTERS, (m - b for m, b in zip(self.mid, self.before)))),
+                   during_trials=dict(zip(COUNTERS, (a - m for a, m in zip(after, self.mid)))),
+                   baseline_s=self.t1 - self.t0, trials_s=t2 - self.t1,
+                   suffix=self.plan.report() if self.plan is not None else {})
+        for k, a, b in zip(("calibrations", "captures", "repacks"), after, self.before):  # totals of the whole call
+            rep[k] = a - b
+        if shard is not None:
+            rep["shard"] = list(shard)
+        return rep
 
 
 def delta_loss_table(net, batches, bits=(8, 6, 4), lnums=None, channels=None, progress=None, suffix=None,
@@ -503,46 +359,21 @@ def delta_loss_table(net, batches, bits=(8, 6, 4), lnums=None, channels=None, pr
     bits = tuple(sorted({int(b) for b in bits}, reverse=True))
     if not bits or bits[-1] < 1 or bits[0] > 16:
         raise ValueError("smpq: bit-widths must be within 1..16")
-    if engine.get_range_mode() != "static":
-        raise ValueError("smpq: delta_loss_table needs the static range mode (engine.set_range_mode)")
-    if engine.get_dp_group() is not None:
-        raise ValueError("smpq: delta_loss_table runs on one GPU (no data-parallel group)")
-    p = next(net.parameters())
-    if not p.is_cuda or net.training or not getattr(net, "fused", True):
-        raise ValueError("smpq: delta_loss_table needs an eval-mode smpq ResNet on the GPU")
-    if isinstance(batches, ResidentSet):
-        batches.bind(p.device)
-    else:
-        batches = list(batches)
-        if not batches or any(not (torch.is_tensor(x) and x.device == p.device) for x, _ in batches):
-            raise ValueError("smpq: batches must be (x, y) pairs with x on the model's device, or a ResidentSet")
-        batches = [(x, torch.as_tensor(y).to(p.device)) for x, y in batches]
+    p, batches = setup("delta_loss_table", net, batches)
     cols = _select(net, lnums, channels)
     owned = None if shard is None else shard_owner(shard[1], lnum=[ln for ln, _, _ in cols]) == shard[0]
 
-    before = {k: stats.get(k, 0) for k in ("calibrations", "graph_captures", "repack")}
-    t0 = time.perf_counter()
-    eval_loss = ordinary_loss(net, batches)
-    cal = engine.model_state(net).ranges
-    hooks = _EngineHooks(net, cal, batches)
-    b, bflags = _unpatched_pass(hooks, batches, p.device)  # captures every graph
-    if any(bflags) or engine._signature(net) != cal.sig:
-        raise RuntimeError("smpq: the baseline of the delta-loss sweep did not hold (overflow or changed weights)")
-    base_loss = b[0] / b[3]
-    plan = _suffix_plan(net, hooks, use_suffix, budget, b, rows=use_rows)
-    mid = {k: stats.get(k, 0) for k in before}
-    t1 = time.perf_counter()  # (the pass above ended in a host read)
+    run = _Run("delta-loss", net, batches, False)
+    eval_loss, base_loss = run.eval_loss, run.base_loss
+    if use_suffix:
+        run.suffix_plan(budget, rows=use_rows)
+    counts = run.start()
 
     groups = []
     by_conv = {}
     for col, (ln, conv, c) in enumerate(cols):
         by_conv.setdefault(ln, (conv, []))[1].append((col, c))
-    with torch.no_grad():
-        const_rows = {}
-        for ln, (conv, chans) in by_conv.items():
-            w2d = conv.weight.detach().reshape(conv.out_channels, -1)
-            const_rows[ln] = (w2d.amax(1) == w2d.amin(1)).tolist()
-    counts = {"patched": 0, "overflowed": 0, "slow": {}, "constant": []}
+    const_rows = {ln: constant_rows(conv) for ln, (conv, _) in by_conv.items()}
     delta = {bit: np.full(len(cols), np.nan, dtype=np.float64) for bit in bits}
     for ln, (conv, chans) in by_conv.items():
         bn = bn_for(net, conv)
@@ -571,45 +402,16 @@ def delta_loss_table(net, batches, bits=(8, 6, 4), lnums=None, channels=None, pr
             trial_stats[tr.bit][tr.col] = row
 
     with torch.no_grad():
-        sweep(groups, batches, hooks, p.device, out, counts, progress, plan)
-    after = {k: stats.get(k, 0) for k in before}
-    t2 = time.perf_counter()  # (so did the last conv's trials)
-    if not counts["slow"] and (engine._signature(net) != cal.sig or engine.model_state(net).ranges is not cal):
-        raise RuntimeError("smpq: the model changed while the delta-loss sweep ran")
+        sweep(groups, batches, run.hooks, p.device, out, counts, progress, run.plan)
     mine = len(cols) if owned is None else int(owned.sum())
-    report = {"trials": mine * len(bits), "patched": counts["patched"], "overflowed": counts["overflowed"],
-              "slow": dict(counts["slow"]), "constant": list(counts["constant"]),
-              "baseline": {k: mid[k] - before[k] for k in before},
-              "during_trials": {k: after[k] - mid[k] for k in before},
-              "baseline_s": t1 - t0, "trials_s": t2 - t1, "suffix": plan.report() if plan is not None else {}}
-    for k in before:  # totals seen during the whole call
-        report[{"graph_captures": "captures", "repack": "repacks"}.get(k, k)] = after[k] - before[k]
-    if shard is not None:
-        report["shard"] = list(shard)
     table = DeltaLossTable(arch_of(net), [ln for ln, _, _ in cols], [c for _, _, c in cols], bits, delta, base_loss,
-                           eval_loss, report)
+                           eval_loss, run.report(mine * len(bits), counts, shard))
     table.stats = trial_stats
     table.owned = owned
     return table
 
 
 # ---- semilayer trials: many rows of one conv per trial -------------------------------
-class Semilayer:
-    """One trial of semilayer_table: ``channels`` (distinct) of conv ``lnum`` at ``bits`` (one
-    bit-width per channel). ``param`` is what functions._make_semilayers accumulates: the sum over
-    the channels of K * (32 - bit) / 32. ``rows``: the hooks' uploaded lists (ops.TrialRows)."""
-    __slots__ = ("index", "lnum", "conv", "channels", "bits", "param", "rows")
-
-    def __init__(self, index, lnum, conv, channels, bits, k_elems):
-        self.index, self.lnum, self.conv = index, lnum, conv
-        self.channels = [int(c) for c in channels]
-        self.bits = [int(b) for b in bits]
-        self.param = 0.0
-        for b in self.bits:  # in the reference's order of accumulation
-            self.param += k_elems * ((32 - b) / 32)
-        self.rows = None
-
-
 class SemilayerTable:
     """One entry per semilayer, in the order given: ``lnum``, ``channels``, ``bits``, ``param``;
     ``loss`` (mean over batches of the batch-mean cross entropy), ``acc`` (top-1), ``kl``
@@ -619,13 +421,16 @@ class SemilayerTable:
     public API. ``base_loss`` / ``eval_loss`` as in DeltaLossTable; ``owned``: None, or the bool
     array of the semilayers a sharded call ran (the others are nan; merge_semilayers)."""
 
-    def __init__(self, arch, sems, base_loss, eval_loss, report=None):
-        n = len(sems)
+    def __init__(self, arch, sems, base_loss, eval_loss, report=None, arrays=None):
+        """``sems``: the Semilayers; or None with ``arrays``: their (lnum, channels, bits, param)."""
+        lnum, channels, bits, param = arrays or ([s.lnum for s in sems], [s.channels for s in sems],
+                                                 [s.bits for s in sems], [s.param for s in sems])
+        n = len(lnum)
         self.arch = arch
-        self.lnum = np.asarray([s.lnum for s in sems], dtype=np.int64)
-        self.channels = [list(s.channels) for s in sems]
-        self.bits = [list(s.bits) for s in sems]
-        self.param = np.asarray([s.param for s in sems], dtype=np.float64)
+        self.lnum = np.asarray(lnum, dtype=np.int64)
+        self.channels = [list(c) for c in channels]
+        self.bits = [list(b) for b in bits]
+        self.param = np.asarray(param, dtype=np.float64)
         self.loss = np.full(n, np.nan, dtype=np.float64)
         self.acc = np.full(n, np.nan, dtype=np.float64)
         self.kl = np.full(n, np.nan, dtype=np.float64)
@@ -640,179 +445,6 @@ class SemilayerTable:
         """delta_loss_table's counters, plus ``rows_patched`` (rows over all patched trials) and
         ``max_rows`` (the largest n of one patch)."""
         return dict(self._report)
-
-
-def run_patched_rows(sems, batches, refs, hooks, table, kl, flags, status, store=None):
-    """The patched semilayer trials of ONE conv, without a host sync; run_patched with n rows per
-    trial. For trial i: patch its rows, forward every batch b and score it against ``refs[b]`` into
-    ``table[i]`` (float64 [4]) and ``kl[i]`` (float64 [2]), OR the replays' flags into ``flags[i]``,
-    restore. ``status[i]`` is the trial's int32 [n] constant-channel words. Hooks: patch(sem, status),
-    restore(sem), forward(x), score_kl(logits, y, ref, row, kl_row), invalidate(sem). ``store``: as
-    in run_patched."""
-    for i, sem in enumerate(sems):
-        failed = False
-        try:
-            hooks.patch(sem, status[i])
-            for (kept, x, y), ref in zip(_walk(batches, store), refs):
-                logits, ovf = hooks.forward(x) if kept is None else hooks.resume(kept, store.block)
-                _or_flags(flags[i], ovf)
-                hooks.score_kl(logits, y, ref, table[i], kl[i])
-        except BaseException:
-            failed = True
-            raise
-        finally:
-            hooks.restore(sem)
-            if failed:
-                hooks.invalidate(sem)
-
-
-def sweep_rows(groups, batches, refs, hooks, device, out, counts, progress=None, plan=None):
-    """sweep for semilayer trials. ``groups``: [(patchable?, [Semilayer, ...]), ...], one group per
-    conv (one host sync per group); ``refs``: the reference softmax per batch. Results go to
-    ``out(sem, loss, acc, kl, slow, row, kl_row)``. A constant channel makes its whole semilayer nan
-    and is listed; an overflowed trial is redone by ``hooks.slow(sem) -> (acc, loss, kl)`` after all
-    patched trials, with the semilayers that are not patchable. ``plan``: as in sweep (its
-    self-check also compares the KL statistics)."""
-    nan = math.nan
-    slow = []
-    done = 0
-    if plan is not None:
-        groups = _by_block(groups, hooks)
-    try:
-        for fast, sems in groups:
-            if not fast:
-                slow += [(sem, "not_patchable") for sem in sems]
-                continue
-            store = None if plan is None else _suffix.enter(plan, hooks, sems[0].conv, batches, device, refs)
-            table = torch.zeros(len(sems), 4, dtype=torch.float64, device=device)
-            kl = torch.zeros(len(sems), 2, dtype=torch.float64, device=device)
-            flags = torch.zeros(len(sems), 2, dtype=torch.int32, device=device)
-            words = torch.zeros(sum(len(s.channels) for s in sems), dtype=torch.int32, device=device)
-            status = list(torch.split(words, [len(s.channels) for s in sems]))
-            run_patched_rows(sems, batches, refs, hooks, table, kl, flags, status, store)
-            rows, kls, fl, st = table.tolist(), kl.tolist(), flags.tolist(), words.tolist()  # the conv's one host sync
-            at = 0
-            for sem, row, klrow, (ovf, stale) in zip(sems, rows, kls, fl):
-                const = [c for c, word in zip(sem.channels, st[at:at + len(sem.channels)]) if word]
-                at += len(sem.channels)
-                if stale:
-                    raise RuntimeError("smpq: the model's weights changed while the semilayer sweep ran")
-                if const:
-                    counts["constant"] += [(sem.lnum, c, sem.bits[sem.channels.index(c)]) for c in const]
-                    out(sem, nan, nan, nan, False, None, None)
-                elif ovf:
-                    counts["overflowed"] += 1
-                    slow.append((sem, "overflow"))
-                else:
-                    counts["patched"] += 1
-                    counts["rows_patched"] += len(sem.channels)
-                    counts["max_rows"] = max(counts["max_rows"], len(sem.channels))
-                    out(sem, row[0] / row[3], row[1] / row[2], klrow[0] / klrow[1], False, row, klrow)
-            done += len(sems)
-            if progress is not None:
-                progress(done, counts)
-    finally:
-        if plan is not None:
-            plan.store.release()
-    for sem, why in slow:
-        counts["slow"][why] = counts["slow"].get(why, 0) + 1
-        acc, loss, klv = hooks.slow(sem)  # (constant channels never get here: semilayer_table lists them first)
-        out(sem, loss, acc, klv, True, None, None)
-        done += 1
-        if progress is not None:
-            progress(done, counts)
-
-
-class _RowsHooks(_EngineHooks):
-    """sweep_rows's hooks on the real engine. ``reference``: what slow trials are compared with."""
-
-    def __init__(self, net, cal, batches, reference):
-        super().__init__(net, cal, batches)
-        self.reference = reference
-        self._rows_save = None
-
-    def prepare(self, sems):
-        """Upload the lists of every semilayer of one conv up front and size the save area."""
-        conv = sems[0].conv
-        self._bind(conv)
-        lw, cout, K = self._plan.codes.shape
-        for sem in sems:
-            sem.rows = ops.trial_rows_lists(sem.channels, sem.bits, cout, self._plan.codes.device)
-        need = ops.trial_rows_save_bytes(lw, K, max(len(s.channels) for s in sems))
-        if self._rows_save is None or self._rows_save.numel() < need or self._rows_save.device != self._plan.codes.device:
-            self._rows_save = torch.empty(need, dtype=torch.int8, device=self._plan.codes.device)
-
-    def patch(self, sem, status):
-        self._bind(sem.conv)
-        self.new_trial()
-        ops.trial_rows_patch(sem.conv.weight.detach(), sem.rows, None, self._a, self._plan.codes, self._wscale,
-                             self._plan.col_scale, self._rows_save, status, km=self._km)
-
-    def restore(self, sem):
-        ops.trial_rows_restore(sem.rows, self._plan.codes, self._wscale, self._plan.col_scale, self._rows_save, km=self._km)
-
-    def invalidate(self, sem):
-        sem.conv._content_gen += 1
-
-    def score_kl(self, logits, y, ref, row, kl_row):
-        probs = ops.softmax_xent(logits.float().contiguous(), y, row, want_probs=True)
-        ops.kl_rows(ref, probs, kl_row)
-
-    def slow(self, sem):
-        """One semilayer through the public API on the model itself: quantize its channels one by
-        one, evaluate as functions.evaluate_acc_loss_softmax does, KL against the reference, put
-        weights and metadata back bitwise. Returns (acc, loss, kl)."""
-        if self._state is None:
-            self._state = checkpoint.snapshot(self.net)
-        try:
-            for c, bit in zip(sem.channels, sem.bits):
-                channel_wise_quantizationperchan(sem.conv.weight.data, bit, c)
-            check_pending()
-            acc, loss, outs = ordinary_eval(self.net, self.batches)
-            return acc, loss, kl_of(self.reference, outs)
-        finally:
-            try:
-                check_pending()
-            except ZeroDivisionError:
-                pass
-            checkpoint.restore_(self.net, self._state)
-
-
-def ordinary_eval(net, batches):
-    """functions.evaluate_acc_loss_softmax on device batches: (top-1 accuracy, mean batch loss, the
-    per-batch softmax outputs), a fresh calibration on the first batch, one host sync."""
-    acc, outs = None, []
-    engine.new_evaluation(net)
-    with torch.no_grad():
-        for x, y in batches:
-            out = net(x).float().contiguous()
-            if acc is None:
-                acc = torch.zeros(4, dtype=torch.float64, device=out.device)
-            outs.append(ops.softmax_xent(out, y, acc, want_probs=True))
-    loss_sum, correct, seen, count = acc.tolist()
-    return correct / seen, loss_sum / count, outs
-
-
-def kl_of(reference, outs):
-    """functions.KLdiv(reference, outs): sum over images of sum_c p * log(p / q), over the images."""
-    st = torch.zeros(2, dtype=torch.float64, device=outs[0].device)
-    for p, q in zip(reference, outs):
-        ops.kl_rows(p.to(q.device), q, st)
-    s, n = st.tolist()
-    return s / n
-
-
-def _unpatched_pass_probs(hooks, batches, device):
-    """_unpatched_pass that also returns each batch's softmax (fresh tensors, outside any graph pool)."""
-    base = torch.zeros(4, dtype=torch.float64, device=device)
-    flags = torch.zeros(2, dtype=torch.int32, device=device)
-    probs = []
-    with torch.no_grad():
-        for x, y in batches:
-            logits, ovf = hooks.forward(x)
-            _or_flags(flags, ovf)
-            probs.append(ops.softmax_xent(logits.float().contiguous(), y, base, want_probs=True))
-    return base.tolist(), flags.tolist(), probs
 
 
 def _semilayers(net, semilayers):
@@ -857,50 +489,26 @@ def semilayer_table(net, batches, semilayers, reference_outputs=None, progress=N
     merge_semilayers joins the parts."""
     shard = check_shard(shard)
     use_suffix, budget = _suffix.switch(suffix, suffix_bytes)
-    if engine.get_range_mode() != "static":
-        raise ValueError("smpq: semilayer_table needs the static range mode (engine.set_range_mode)")
-    if engine.get_dp_group() is not None:
-        raise ValueError("smpq: semilayer_table runs on one GPU (no data-parallel group)")
-    p = next(net.parameters())
-    if not p.is_cuda or net.training or not getattr(net, "fused", True):
-        raise ValueError("smpq: semilayer_table needs an eval-mode smpq ResNet on the GPU")
-    if isinstance(batches, ResidentSet):
-        batches.bind(p.device)
-    else:
-        batches = list(batches)
-        if not batches or any(not (torch.is_tensor(x) and x.device == p.device) for x, _ in batches):
-            raise ValueError("smpq: batches must be (x, y) pairs with x on the model's device, or a ResidentSet")
-        batches = [(x, torch.as_tensor(y).to(p.device)) for x, y in batches]
+    p, batches = setup("semilayer_table", net, batches)
     sems = _semilayers(net, semilayers)
     owned = None if shard is None else shard_owner(shard[1], count=len(sems)) == shard[0]
     if reference_outputs is not None:
         reference_outputs = [r.to(p.device) for r in reference_outputs]
 
-    before = {k: stats.get(k, 0) for k in ("calibrations", "graph_captures", "repack")}
-    t0 = time.perf_counter()
-    _, eval_loss, eval_outs = ordinary_eval(net, batches)
-    cal = engine.model_state(net).ranges
-    hooks = _RowsHooks(net, cal, batches, eval_outs if reference_outputs is None else reference_outputs)
-    b, bflags, base_probs = _unpatched_pass_probs(hooks, batches, p.device)  # captures every graph
-    if any(bflags) or engine._signature(net) != cal.sig:
-        raise RuntimeError("smpq: the baseline of the semilayer sweep did not hold (overflow or changed weights)")
-    base_loss = b[0] / b[3]
-    if reference_outputs is not None and len(reference_outputs) != len(base_probs):  # (a ResidentSet has no len)
+    run = _Run("semilayer", net, batches, True)
+    hooks = run.hooks
+    if reference_outputs is not None and len(reference_outputs) != len(run.base_probs):  # (a ResidentSet has no len)
         raise ValueError("smpq: reference_outputs must hold one softmax tensor per batch")
-    refs = base_probs if reference_outputs is None else reference_outputs
+    # what slow trials are compared with, and the patched ones
+    hooks.reference = run.eval_outs if reference_outputs is None else reference_outputs
+    refs = run.base_probs if reference_outputs is None else reference_outputs
     if reference_outputs is not None:
-        del eval_outs
-    plan = None
+        run.eval_outs = None
     if use_suffix:  # what a block's self-check must reproduce: the unpatched pass's KL statistics too
-        base_kl = torch.zeros(2, dtype=torch.float64, device=p.device)
-        for ref, probs in zip(refs, base_probs):
-            ops.kl_rows(ref, probs, base_kl)
-        plan = _suffix_plan(net, hooks, True, budget, b, base_kl.tolist())
-    mid = {k: stats.get(k, 0) for k in before}
-    t1 = time.perf_counter()
+        run.suffix_plan(budget, kl_stats(refs, run.base_probs))
+    counts = dict(run.start(), rows_patched=0, max_rows=0)
 
-    counts = {"patched": 0, "overflowed": 0, "slow": {}, "constant": [], "rows_patched": 0, "max_rows": 0}
-    table = SemilayerTable(arch_of(net), sems, base_loss, eval_loss)
+    table = SemilayerTable(arch_of(net), sems, run.base_loss, run.eval_loss)
     table.owned = owned
     by_conv = {}
     for sem in sems:
@@ -911,13 +519,12 @@ def semilayer_table(net, batches, semilayers, reference_outputs=None, progress=N
         for ln, group in by_conv.items():
             conv = group[0].conv
             bn = bn_for(net, conv)
-            w2d = conv.weight.detach().reshape(conv.out_channels, -1)
-            const_rows = (w2d.amax(1) == w2d.amin(1)).tolist()
+            const_rows = constant_rows(conv)
             fast, rest = [], []
             for sem in group:
-                const = [c for c in sem.channels if const_rows[c]]
+                const = [(ln, c, b) for c, b in zip(sem.channels, sem.bits) if const_rows[c]]
                 if const:  # the reference raises there (functions.py:40): the whole semilayer nan, listed
-                    counts["constant"] += [(ln, c, sem.bits[sem.channels.index(c)]) for c in const]
+                    counts["constant"] += const
                 elif patchable_rows(conv, bn, sem.channels):
                     fast.append(sem)
                 else:
@@ -935,22 +542,8 @@ def semilayer_table(net, batches, semilayers, reference_outputs=None, progress=N
             table.stats[i], table.kl_stats[i] = row, kl_row
 
     with torch.no_grad():
-        sweep_rows(groups, batches, refs, hooks, p.device, out, counts, progress, plan)
-    after = {k: stats.get(k, 0) for k in before}
-    t2 = time.perf_counter()
-    if not counts["slow"] and (engine._signature(net) != cal.sig or engine.model_state(net).ranges is not cal):
-        raise RuntimeError("smpq: the model changed while the semilayer sweep ran")
-    report = {"trials": len(sems) if owned is None else int(owned.sum()), "patched": counts["patched"],
-              "overflowed": counts["overflowed"], "slow": dict(counts["slow"]), "constant": list(counts["constant"]),
-              "rows_patched": counts["rows_patched"], "max_rows": counts["max_rows"],
-              "baseline": {k: mid[k] - before[k] for k in before},
-              "during_trials": {k: after[k] - mid[k] for k in before},
-              "baseline_s": t1 - t0, "trials_s": t2 - t1, "suffix": plan.report() if plan is not None else {}}
-    for k in before:
-        report[{"graph_captures": "captures", "repack": "repacks"}.get(k, k)] = after[k] - before[k]
-    if shard is not None:
-        report["shard"] = list(shard)
-    table._report = report
+        sweep(groups, batches, hooks, p.device, out, counts, progress, run.plan, refs)
+    table._report = run.report(len(sems) if owned is None else int(owned.sum()), counts, shard)
     return table
 
 
@@ -963,11 +556,16 @@ def _same_bits(a, b):
     return np.float64(a).tobytes() == np.float64(b).tobytes()
 
 
+def _parts(tables):
+    tables = list(tables)
+    if not tables:
+        raise ValueError("smpq: nothing to merge")
+    return tables
+
+
 def _merge_owned(tables, n, what):
     """The part that owns each of ``n`` columns (int array), after checking the parts' baselines and
     that their ``owned`` masks are disjoint and cover every column (None counts as all true)."""
-    if not tables:
-        raise ValueError("smpq: nothing to merge")
     first = tables[0]
     for i, t in enumerate(tables):
         if t.arch != first.arch:
@@ -1020,9 +618,7 @@ def merge_delta_loss(tables):
     equal as bits in every part, and the ``owned`` masks are disjoint and cover every column.
     report(): trials, patched, overflowed and slow summed, constant concatenated and sorted,
     ``world``, ``ranks`` (the parts' reports in rank order), baseline_s / trials_s the maximum."""
-    tables = list(tables)
-    if not tables:
-        raise ValueError("smpq: nothing to merge")
+    tables = _parts(tables)
     first = tables[0]
     for i, t in enumerate(tables):
         if t.bits != first.bits:
@@ -1055,9 +651,7 @@ def merge_semilayers(tables):
     ``acc``, ``kl``, ``stats``, ``kl_stats`` and ``slow`` of every semilayer come from the part that
     owns it. The parts must list the same semilayers (lnum, channels, bits). report() also sums
     ``rows_patched`` and takes the maximum of ``max_rows``."""
-    tables = list(tables)
-    if not tables:
-        raise ValueError("smpq: nothing to merge")
+    tables = _parts(tables)
     first = tables[0]
     for i, t in enumerate(tables):
         if len(t.channels) != len(first.channels):
@@ -1067,10 +661,8 @@ def merge_semilayers(tables):
                 raise ValueError("smpq: semilayer %d of part %d is not part 0's" % (j, i))
     n = len(first.channels)
     part = _merge_owned(tables, n, "semilayer")
-    # (SemilayerTable reads lnum, channels, bits and param of each entry, nothing else)
-    sems = [types.SimpleNamespace(lnum=int(first.lnum[j]), channels=first.channels[j], bits=first.bits[j],
-                                  param=float(first.param[j])) for j in range(n)]
-    out = SemilayerTable(first.arch, sems, first.base_loss, first.eval_loss)
+    out = SemilayerTable(first.arch, None, first.base_loss, first.eval_loss,
+                         arrays=(first.lnum, first.channels, first.bits, first.param))
     for i, t in enumerate(tables):
         mine = part == i
         for name in ("loss", "acc", "kl", "stats", "kl_stats", "slow"):

@@ -22,7 +22,12 @@ block's LAST conv changes one channel of the next block's input, so the block's 
 computes the patched channel alone into it (``rows_conv``, ops.trial_rows_conv), resumes from the
 next block and puts the bytes back (``rows_restore``). The one edit outside this module is
 engine.block_forward's optional ``keep`` tap.
+
+``score_pass`` is the one loop over a table's or a session's batches: it walks the store (or the
+plain batches) and picks each batch's forward. The hooks it calls on the real engine are
+smpq.trials.EngineHooks; this module imports neither smpq.trials nor smpq.sensitivity.
 """
+import itertools
 import os
 import sys
 import time
@@ -30,7 +35,6 @@ import time
 import torch
 
 from . import assignments, engine, ops, prefix
-from .qconv import stats
 
 # SMPQ_TRIAL_SUFFIX=1: delta_loss_table / semilayer_table run their trials through this module
 # (read at import, off by default, announced once on stderr at first use)
@@ -170,43 +174,12 @@ def rows_bytes(net, x, j):
             + ops.trial_rows_conv_save_bytes(limbs, n * h * w, 1))
 
 
-def fill(net, x, cal, j):
-    """Stem + blocks 0..j-1 of batch ``x`` under the installed StaticRanges ``cal``, slice by slice
-    on the current stream: the Kept input of block ``j``, or None when it cannot be resumed from
-    (block j-1 handed on a chained conv1 output, or the input is not limb planes with a static
-    range and nothing else). An overflow in the prefix is not looked at: the table's unpatched
-    pass ran the same launches on the same data and held."""
+def _prefix_pass(net, x, cal, j, tap):
+    """The one prefix pass behind fill and fill_rows: stem + blocks 0..j-1 of batch ``x`` under the
+    installed StaticRanges ``cal``, slice by slice on the current stream, and with ``tap`` on through
+    block ``j`` with engine.block_forward's tap. (Kept or None, why): fill_rows' return values."""
     assert not torch.cuda.is_current_stream_capturing()
     blocks = engine._blocks(net)
-    if not 0 <= j < len(blocks):
-        raise ValueError("smpq suffix: block %d outside 0..%d" % (j, len(blocks) - 1))
-    n = x.shape[0]
-    ctx = engine.Ctx(n, x.device, ranges=cal.by_conv, cache=cal.tensors)
-    parts = []
-    try:
-        for lane, (s0, s1) in enumerate(slices(n)):
-            ctx.n, ctx.lane = s1 - s0, lane
-            act, t1 = engine.stem_forward(net, x[s0:s1], ctx), None
-            for i in range(j):
-                act, t1 = engine.block_forward(blocks[i], act, ctx, last=False, t1=t1, nxt=blocks[i + 1])
-            if t1 is not None or act.q is None or act.rng is None or act.f32 is not None:
-                return None
-            parts.append((s0, s1, act.q, act.rng))
-    finally:
-        ctx.n, ctx.lane = n, None
-    return Kept(parts, n)
-
-
-def fill_rows(net, x, cal, j):
-    """fill(net, x, cal, j) whose one pass goes on through block ``j`` with engine.block_forward's tap:
-    (Kept or None, why). ``why`` is None when ``kept.rows`` holds the rows route's tensors, else the
-    reason it does not: "no_tap" (the last conv ran in a chain or fused-downsample launch, or not
-    from and to static limb planes) or "next_not_resumable" (block j + 1's input fails fill's rule).
-    The Kept itself is fill's, whatever ``why``."""
-    assert not torch.cuda.is_current_stream_capturing()
-    blocks = engine._blocks(net)
-    if not 0 <= j < len(blocks) - 1:
-        raise ValueError("smpq suffix: block %d has no next block to write into" % j)
     n = x.shape[0]
     ctx = engine.Ctx(n, x.device, ranges=cal.by_conv, cache=cal.tensors)
     parts, taps, nparts, why = [], [], [], None
@@ -219,7 +192,7 @@ def fill_rows(net, x, cal, j):
             if t1 is not None or act.q is None or act.rng is None or act.f32 is not None:
                 return None, None
             parts.append((s0, s1, act.q, act.rng))
-            if why is None:
+            if tap and why is None:
                 keep = {}
                 out, t1 = engine.block_forward(blocks[j], act, ctx, last=False, t1=None, nxt=blocks[j + 1], keep=keep)
                 if "x" not in keep:
@@ -232,9 +205,31 @@ def fill_rows(net, x, cal, j):
     finally:
         ctx.n, ctx.lane = n, None
     kept = Kept(parts, n)
-    if why is None:
+    if tap and why is None:
         kept.rows = RowsKept(taps, Kept(nparts, n), kept)
     return kept, why
+
+
+def fill(net, x, cal, j):
+    """Stem + blocks 0..j-1 of batch ``x`` under the installed StaticRanges ``cal``, slice by slice
+    on the current stream: the Kept input of block ``j``, or None when it cannot be resumed from
+    (block j-1 handed on a chained conv1 output, or the input is not limb planes with a static
+    range and nothing else). An overflow in the prefix is not looked at: the table's unpatched
+    pass ran the same launches on the same data and held."""
+    if not 0 <= j < len(engine._blocks(net)):
+        raise ValueError("smpq suffix: block %d outside 0..%d" % (j, len(engine._blocks(net)) - 1))
+    return _prefix_pass(net, x, cal, j, False)[0]
+
+
+def fill_rows(net, x, cal, j):
+    """fill(net, x, cal, j) whose one pass goes on through block ``j`` with engine.block_forward's tap:
+    (Kept or None, why). ``why`` is None when ``kept.rows`` holds the rows route's tensors, else the
+    reason it does not: "no_tap" (the last conv ran in a chain or fused-downsample launch, or not
+    from and to static limb planes) or "next_not_resumable" (block j + 1's input fails fill's rule).
+    The Kept itself is fill's, whatever ``why``."""
+    if not 0 <= j < len(engine._blocks(net)) - 1:
+        raise ValueError("smpq suffix: block %d has no next block to write into" % j)
+    return _prefix_pass(net, x, cal, j, True)
 
 
 def last_conv(net, j):
@@ -473,7 +468,7 @@ def enter(plan, hooks, conv, batches, device, refs=None):
     if not st.kept:
         return None
     # the self-check: no patch, through the suffix, against the table's unpatched replay pass
-    same, got = _unpatched(plan, st, hooks, batches, device, refs, j, False)
+    same, got = _unpatched(plan, st, hooks, batches, device, refs, False)
     row["self_check"], row["self_check_s"] = same, time.perf_counter() - t0 - row["prefix_pass_s"]
     if not same:
         st.release()
@@ -484,7 +479,7 @@ def enter(plan, hooks, conv, batches, device, refs=None):
         # inputs of block j + 1 resume to the same statistics
         t1 = time.perf_counter()
         planes = hooks.rows_check(st, j)
-        same, got = _unpatched(plan, st, hooks, batches, device, refs, j, True)
+        same, got = _unpatched(plan, st, hooks, batches, device, refs, True)
         row["rows_self_check"], row["rows_self_check_s"] = bool(planes and same), time.perf_counter() - t1
         if not (planes and same):
             st.release()
@@ -495,133 +490,45 @@ def enter(plan, hooks, conv, batches, device, refs=None):
     return st
 
 
-def _unpatched(plan, st, hooks, batches, device, refs, j, rows):
+def score_pass(hooks, batches, store, refs, row, kl_row, flags, rows_channel=None, rows_from_next=False, probs=None):
+    """THE loop over the batches: forward every batch and score it into ``row``
+    (float64 [4]), ORing the forwards' flag pairs into ``flags`` (int32 [2]). Every trial, self-check
+    and unpatched pass of the tables and the session comes here. ``store`` (a Store or None): a batch
+    it keeps runs through hooks.resume(kept, store.block) from its kept block input instead of
+    hooks.forward(x); with ``rows_channel`` a batch that has ``kept.rows`` runs through
+    hooks.resume_rows(kept, store.block, rows_channel), with ``rows_from_next`` through
+    hooks.resume(kept.rows.next, store.block + 1) (the rows route's self-check). ``refs`` (one
+    reference softmax per batch, or None): with them a batch is scored by hooks.score_kl(logits, y,
+    ref, row, kl_row), without by hooks.score(logits, y, row). ``probs`` (a list or None): grows by
+    each batch's softmax, hooks.score(logits, y, row, True)'s, for the baseline that needs them."""
+    walk = ((None, x, y) for x, y in batches) if store is None else store.walk(batches)
+    for (kept, x, y), ref in zip(walk, itertools.repeat(None) if refs is None else refs):
+        if kept is None:
+            logits, ovf = hooks.forward(x)
+        elif rows_channel is not None and kept.rows is not None:
+            logits, ovf = hooks.resume_rows(kept, store.block, rows_channel)
+        elif rows_from_next and kept.rows is not None:
+            logits, ovf = hooks.resume(kept.rows.next, store.block + 1)
+        else:
+            logits, ovf = hooks.resume(kept, store.block)
+        torch.bitwise_or(flags, ovf, out=flags)
+        if probs is not None:
+            probs.append(hooks.score(logits, y, row, True))
+        elif refs is None:
+            hooks.score(logits, y, row)
+        else:
+            hooks.score_kl(logits, y, ref, row, kl_row)
+    for _ in walk:  # (run the generator to its end: Store.walk's batch-count check)
+        pass
+
+
+def _unpatched(plan, st, hooks, batches, device, refs, rows):
     """One unpatched pass over the store's batches: (does it reproduce the plan's base statistics
     bitwise with zero flags?, the statistics). ``rows``: a batch with a RowsKept resumes from its
-    kept input of block j + 1 instead of block j's."""
+    kept input of the next block instead of the store's."""
     got = torch.zeros(4, dtype=torch.float64, device=device)
     kl = torch.zeros(2, dtype=torch.float64, device=device)
     flags = torch.zeros(2, dtype=torch.int32, device=device)
-    walk = st.walk(batches)
-    for (kept, x, y), ref in zip(walk, refs if refs is not None else _nones()):
-        if kept is None:
-            logits, ovf = hooks.forward(x)
-        elif rows and kept.rows is not None:
-            logits, ovf = hooks.resume(kept.rows.next, j + 1)
-        else:
-            logits, ovf = hooks.resume(kept, j)
-        torch.bitwise_or(flags, ovf, out=flags)
-        if refs is None:
-            hooks.score(logits, y, got)
-        else:
-            hooks.score_kl(logits, y, ref, got, kl)
-    for _ in walk:  # (run the generator to its end: its batch-count check)
-        pass
+    score_pass(hooks, batches, st, refs, got, kl, flags, rows_from_next=rows)
     same = got.tolist() == plan.base and (refs is None or kl.tolist() == plan.base_kl) and not any(flags.tolist())
     return same, got.tolist()
-
-
-def _nones():
-    while True:
-        yield None
-
-
-class EngineHooks:
-    """enter's and the trials' hooks on the real engine (mixed into sensitivity's hooks, which give
-    ``net`` and ``cal``). ``resume`` looks ``suffix.resume`` up at call time and enqueues the content
-    check for the first resumed batch after every ``new_trial``."""
-    plan = None
-    _check = True
-
-    def block_of(self, conv):
-        return block_of(self.net, conv)
-
-    def block_name(self, j):
-        return prefix.block_names(self.net)[j]
-
-    def kept_bytes(self, x, j):
-        return kept_bytes(self.net, x, j)
-
-    def fill(self, x, j):
-        return fill(self.net, x, self.cal, j)
-
-    def new_trial(self):
-        self._check = True
-
-    def resume(self, kept, j):
-        before = stats["hip_conv"]
-        out = resume(self.net, kept, self.cal, j, check=self._check)
-        self._check = False
-        if self.plan is not None:
-            self.plan.resumed += 1
-            self.plan.launches += stats["hip_conv"] - before
-        return out
-
-    def sync(self):
-        torch.cuda.synchronize()
-
-    # ---- the rows route (DESIGN.md 5j) ----
-    def last_conv(self, j):
-        return last_conv(self.net, j)[0]
-
-    def rows_block(self, j):
-        """None when block ``j``'s last conv may go the rows route, else why not."""
-        from . import sensitivity  # (sensitivity imports this module)
-        if j >= len(engine._blocks(self.net)) - 1:
-            return "last_block"  # its output is fp32 for the average pool
-        conv, bn = last_conv(self.net, j)
-        if not rows_geometry(conv):
-            return "geometry"
-        return None if sensitivity.patchable(conv, bn) else "not_patchable"
-
-    def rows_bytes(self, x, j):
-        return rows_bytes(self.net, x, j)
-
-    def fill_rows(self, x, j):
-        return fill_rows(self.net, x, self.cal, j)
-
-    _row_list = None
-
-    def _one_row(self, j, channel, device):
-        """The uploaded one-entry list of a trial's channel (made once per trial, not per batch)."""
-        key = (j, int(channel), device)
-        if self._row_list is None or self._row_list[0] != key:
-            self._row_list = (key, ops.trial_rows_lists([int(channel)], 8, last_conv(self.net, j)[0].out_channels,
-                                                        device, "trial_rows_conv"))
-        return self._row_list[1]
-
-    def rows_check(self, st, j):
-        """The one-row conv of channel 0 from the UNPATCHED operand into every kept input of block
-        j + 1: the bytes it replaced must be the bytes it wrote (compared on the device, one host
-        read), and it must not flag an overflow."""
-        dev = next(e for e in st.entries if e is not None).parts[0][2].device
-        rows = self._one_row(j, 0, dev)
-        bad = torch.zeros(2, dtype=torch.int32, device=dev)
-        for e in st.entries:
-            if e is None or e.rows is None:
-                continue
-            done = []
-            try:
-                rows_conv(self.net, e, j, rows, bad[:1], done)
-                for save, (_, _, q, _) in zip(e.rows.saves, e.rows.next.parts):
-                    old = save[:q.shape[0] * q[0, ..., 0].numel()].view(q.shape[0], -1)
-                    bad[1:] |= (old != q.reshape(q.shape[0], -1, q.shape[-1])[:, :, 0]).any().to(torch.int32)
-            finally:
-                rows_restore(e, rows, done)
-        return not any(bad.tolist())
-
-    def resume_rows(self, kept, j, channel):
-        """A trial's forward of one batch on the rows route: channel ``channel`` of block ``j``'s last
-        conv from its patched operand into the kept input of block j + 1, the resumed forward from
-        there, the old bytes back (whatever happens): (logits, flags with the one-row conv's overflow
-        in word 0)."""
-        flag = torch.zeros(2, dtype=torch.int32, device=kept.parts[0][2].device)
-        rows = self._one_row(j, channel, flag.device)
-        done = []
-        try:
-            rows_conv(self.net, kept, j, rows, flag[:1], done)
-            logits, ovf = self.resume(kept.rows.next, j + 1)
-            torch.bitwise_or(flag, ovf, out=flag)
-        finally:
-            rows_restore(kept, rows, done)
-        return logits, flag

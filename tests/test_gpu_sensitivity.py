@@ -293,3 +293,53 @@ def test_deltas_against_the_oracle(gpu, knobs):
             assert abs(got - ref) <= bound, (ln, c, got, ref, bound)
             assert (got > 0) == (ref > 0), (ln, c, got, ref)
     assert compared >= 3, "only %d of the 12 oracle deltas reach ten times the bound" % compared
+
+
+# ---- one trial, three callers ----------------------------------------------------------------------------
+@pytest.mark.parametrize("resumed", [False, True])
+def test_the_three_callers_run_the_same_trial(gpu, knobs, resumed):
+    """The tables and the session share one trial loop (trials.guarded_trial, suffix.score_pass), so
+    the same channel at the same bit-width gives the same four statistics, as float64 bits, whether
+    it is a delta_loss_table column, a one-channel semilayer of semilayer_table or a Session trial:
+    a first conv, a mid conv and the last conv of a block at suffix.first_block, by replay
+    (``resumed`` off) and resumed (the delta-loss side with the rows route, which that last conv
+    takes). The model and its packed operands are left bitwise as they were."""
+    from smpq import engine, ops, search, sensitivity, suffix
+    engine.USE_GRAPH[0] = True
+    ops.set_act_limbs(3)
+    _, dev = _batches(gpu, n=4)
+    net = build_model(gpu, "resnet18", None, "r18_u8_cal")
+    last = 2 * (suffix.first_block(net) + 1)  # conv2 of the first resumed BasicBlock
+    picks = [(1, 7), (8, 100), (last, 33)]
+    sd = {k: v.detach().clone() for k, v in net.state_dict().items()}
+    sensitivity.ordinary_loss(net, dev)  # packs every operand
+    ops_before = _operands(net)
+    copies = {k: [t.clone() for t in ts] for k, ts in ops_before.items()}
+    assert len(ops_before) >= 17
+
+    delta = sensitivity.delta_loss_table(net, dev, bits=(4,), lnums=[ln for ln, _ in picks],
+                                         channels={ln: [c] for ln, c in picks}, suffix=resumed, rows=resumed)
+    semi = sensitivity.semilayer_table(net, dev, [(ln, [c], 4) for ln, c in picks], suffix=resumed)
+    with search.Session(net, dev, boundaries=None if resumed else ()) as s:
+        results = [s.trial(ln, [c], 4) for ln, c in picks]
+    assert delta.report()["patched"] == 3 and semi.report()["patched"] == 3
+    assert [r.route for r in results] == ["patched"] * 3
+    if resumed:
+        blocks = {b["block"]: b for b in delta.report()["suffix"]["blocks"]}
+        assert blocks[last // 2 - 1]["rows"] == "used" and blocks[last // 2 - 1]["rows_trials"] == 1
+        assert semi.report()["suffix"]["resumed_forwards"] > 0 and results[2].resumed_from is not None
+    for i, (ln, c) in enumerate(picks):
+        assert (int(delta.lnum[i]), int(delta.cnum[i]), int(semi.lnum[i])) == (ln, c, ln)
+        a = np.asarray(delta.stats[4][i], dtype=np.float64).tobytes()
+        b = np.asarray(semi.stats[i], dtype=np.float64).tobytes()
+        d = np.asarray(results[i].stats, dtype=np.float64).tobytes()
+        print("lnum %d channel %d: %r %r %r" % (ln, c, delta.stats[4][i].tolist(), semi.stats[i].tolist(), results[i].stats))
+        assert a == b == d, (ln, c)
+        assert not np.isnan(delta.stats[4][i]).any()
+    for k, v in net.state_dict().items():
+        assert torch.equal(v, sd[k]), k
+    now = _operands(net)
+    assert now.keys() == ops_before.keys()
+    for k, ts in now.items():
+        for t, t0, cp in zip(ts, ops_before[k], copies[k]):
+            assert t is t0 and torch.equal(t, cp), k

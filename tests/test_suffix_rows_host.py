@@ -177,13 +177,13 @@ def test_restore_order_when_the_resumed_forward_fails(built_lib, monkeypatch):
     """The real EngineHooks.resume_rows around injected launches: the kept planes are put back first
     (only the slices that were written), then the operand, then the conv is invalidated, and the
     sweep releases the store."""
-    from smpq import suffix
+    from smpq import suffix, trials
 
     log = []
 
-    class Hooks(RowsHooks, suffix.EngineHooks):
+    class Hooks(RowsHooks, trials.EngineHooks):
         net = None
-        resume_rows = suffix.EngineHooks.resume_rows
+        resume_rows = trials.EngineHooks.resume_rows
 
         def _one_row(self, j, channel, device):
             return ("rows", j, channel)
@@ -227,6 +227,40 @@ def test_restore_order_when_the_resumed_forward_fails(built_lib, monkeypatch):
                    "invalidate"]
     assert released[-1] == log and c2._content_gen == 1  # the store went after both restores
     assert plan.store.entries == [] and plan.store.rows is None
+
+
+def test_semilayer_trials_of_the_rows_conv_resume_from_the_block(built_lib):
+    """The one loop serves both tables, so this pins who takes the rows route: a semilayer sweep
+    (with refs) over a block's last conv, through a plan with rows=True whose store holds the route's
+    tensors, still resumes every batch from block j (a semilayer of one channel too): the route is
+    for the single-row trials (Trial) of the store's ``rows`` conv. Both self-checks run, and compare
+    the KL statistics as well."""
+    from smpq import sensitivity, suffix
+    c2 = FakeConv(6)
+    refs = [0.25, 0.5]
+    sems = [sensitivity.Semilayer(0, 1, c2, [0, 1], [8, 8], 64), sensitivity.Semilayer(1, 1, c2, [3], [4], 64)]
+    counts = {"patched": 0, "overflowed": 0, "slow": {}, "constant": [], "rows_patched": 0, "max_rows": 0}
+    hooks = RowsHooks({6: c2})
+    plan = suffix.Plan(None, [2.0, 0.0, 2.0, 2.0], [0.75, 2.0], first=0, rows=True)
+    got = {}
+    sensitivity.sweep([(True, sems)], BATCHES, hooks, "cpu",
+                      lambda sem, loss, acc, kl, slow, row, kl_row: got.__setitem__(sem.index, (loss, kl, slow)),
+                      counts, plan=plan, refs=refs)
+    assert got == {0: (6000.0, 0.375, False), 1: (6001.0, 0.375, False)}
+    assert counts["patched"] == 2 and counts["rows_patched"] == 3 and counts["max_rows"] == 2
+    assert not [e for e in hooks.log if e[0] == "resume_rows"]
+    seq = [e[:2] for e in hooks.log if e[0] in ("resume", "rows_check")]
+    assert seq == [("resume", 6)] * 2 + [("rows_check", 6)] + [("resume", 7)] * 2 + [("resume", 6)] * 4
+    assert [e[0] for e in hooks.log if e[0] in ("patch", "restore")] == ["patch", "restore"] * 2
+    (b,) = plan.report()["blocks"]
+    assert (b["rows"], b["rows_kept"], b["rows_trials"], b["self_check"], b["rows_self_check"]) == ("used", 2, 0, True, True)
+    assert plan.store.entries == [] and plan.store.rows is None
+    # the KL statistics are part of the self-check: another base_kl fails it before any trial
+    hooks = RowsHooks({6: c2})
+    plan = suffix.Plan(None, [2.0, 0.0, 2.0, 2.0], [0.5, 2.0], first=0, rows=True)
+    with pytest.raises(RuntimeError, match="does not reproduce"):
+        sensitivity.sweep([(True, sems)], BATCHES, hooks, "cpu", lambda *a: None, dict(counts), plan=plan, refs=refs)
+    assert not [e for e in hooks.log if e[0] == "patch"] and plan.store.entries == []
 
 
 def test_env_switch(built_lib, monkeypatch, capsys):
