@@ -710,6 +710,45 @@ int smpq_trial_rows_conv_q_host(const int8_t* xq, const float* x_absmax, int n, 
 int smpq_trial_rows_conv_restore_host(const int32_t* channels, int nrows, int limbs, int64_t pixels, int cout,
                                       int8_t* yq, const void* save);
 
+/* ---- grouped 3x3 conv (additions to ABI 7) -------------------------------------------------------
+ * The conv2 of a ResNeXt Bottleneck (resnet.py:75-78 with groups > 1): weight [cout][cg][3][3],
+ * cg = cin / groups, og = cout / groups; output channel c reads input channels (c / og) * cg .. + cg.
+ * A 16-output-channel fragment of the kernel covers max(1, 16 / og) groups and reads
+ * S = cg * max(1, 16 / og) consecutive input channels.
+ * smpq_conv2d_grouped_supported: 1 for groups >= 2, 3x3 / pad 1 / stride 1 or 2, limbs == 3,
+ *   wlimbs 1 or 3, cin % 16 == 0, cout % 16 == 0, og dividing 16 or divided by 16, S one of 16, 32,
+ *   64, and a halo patch of the 64-output-channel workgroup's input channels that fits LDS; else 0.
+ * smpq_pack_weights_grouped: the per-row arithmetic of smpq_pack_weights_ex (step, wlimbs, offset,
+ *   wscale, status as there) on w [cout][cg][kh][kw] for any cg: compact codes [wlimbs][cout][kh*kw*cg],
+ *   k = tap * cg + ci.
+ * smpq_weights_grouped_expand: compact 3x3 codes -> the fragment-ordered block-diagonal copy the
+ *   kernel keeps in registers, out [planes][cout / 16][NK][64][16] int8 of
+ *   smpq_weights_grouped_expand_bytes bytes (0 for an unsupported operand), 16-B aligned: byte b of
+ *   lane i of step j of fragment f is code (row 16 f + i % 16, k = 64 j + 16 (i / 16) + b), k ordered
+ *   [tap][s] over the fragment's S channels, NK = ceil(9 S / 64) steps; zero outside the row's own
+ *   group and in the K padding. wlimbs == 1 adds one plane, the group indicator (1 where a code may
+ *   be non-zero), from which the kernel forms the per-group window sums the weight offsets multiply.
+ *   The copy is derived from the codes and must be rebuilt whenever they change.
+ * smpq_conv2d_grouped_fwd_q: smpq_conv2d_fwd_q without a residual and without a tile choice:
+ *   y = relu?(conv_real * col_scale[c] + col_shift[c]) as fp32 NHWC y and / or limb planes yq at the
+ *   static yq_range with the overflow flag; y_absmax optional. codes (compact) and codes_expanded
+ *   describe the same weights; the kernel reads the expanded copy. All three activation planes
+ *   together, and each output tensor, stay below 2 GiB (SMPQ_E_SHAPE otherwise: split the batch).
+ *   SMPQ_E_SHAPE for a geometry smpq_conv2d_grouped_supported refuses, SMPQ_E_INVALID for null or
+ *   misaligned (16 B) pointers or other limb counts, before any launch. */
+int smpq_conv2d_grouped_supported(int cin, int cout, int groups, int kh, int kw, int stride, int pad, int limbs,
+                                  int wlimbs);
+int smpq_pack_weights_grouped(const float* w, int cout, int cg, int kh, int kw, const float* step, int wlimbs,
+                              int8_t* codes, int32_t* offset, float* wscale, int32_t* status, smpq_stream_t stream);
+size_t smpq_weights_grouped_expand_bytes(int wlimbs, int cout, int cg, int groups);
+int smpq_weights_grouped_expand(const int8_t* codes, int wlimbs, int cout, int cg, int groups, int8_t* out,
+                                smpq_stream_t stream);
+int smpq_conv2d_grouped_fwd_q(const int8_t* xq, const float* x_absmax, int n, int h, int w, int cin,
+                              const int8_t* codes, const int8_t* codes_expanded, int wlimbs, const int32_t* offset,
+                              int cout, int groups, int kh, int kw, int stride, int pad, const float* col_scale,
+                              const float* col_shift, int relu, int limbs, float* y, float* y_absmax, int8_t* yq,
+                              float yq_range, int32_t* overflow, smpq_stream_t stream);
+
 /* Diagnostics: one v_mfma_i32_16x16x64_i8 with the kernel's fragment mapping.
  *   a [16][64] int8 row-major, b [16][64] int8 (b[col][k]), c [16][16] int32 row-major */
 int smpq_debug_mfma_i8(const int8_t* a, const int8_t* b, int32_t* c, smpq_stream_t stream);

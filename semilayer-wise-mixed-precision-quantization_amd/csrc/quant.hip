@@ -614,6 +614,22 @@ extern "C" int smpq_pack_weights_ex(const float* w, int cout, int cin, int kh, i
   return check_hip(hipGetLastError(), "pack_weights_ex_kernel launch");
 }
 
+// A grouped conv's weight [cout][cg][kh][kw]: the rows of smpq_pack_weights_ex over the cg channels
+// of the row's own group (any cg), compact codes [wlimbs][cout][kh*kw*cg].
+extern "C" int smpq_pack_weights_grouped(const float* w, int cout, int cg, int kh, int kw, const float* step,
+                                         int wlimbs, int8_t* codes, int32_t* offset, float* wscale, int32_t* status,
+                                         smpq_stream_t stream) {
+  if (!w || !codes || !wscale || !status || cout <= 0 || cg <= 0 || kh <= 0 || kw <= 0)
+    return fail(SMPQ_E_INVALID, "smpq_pack_weights_grouped: bad arguments");
+  if (wlimbs < 1 || wlimbs > 3) return fail(SMPQ_E_INVALID, "smpq_pack_weights_grouped: wlimbs must be 1, 2 or 3");
+  if (wlimbs == 1 && (!step || !offset))
+    return fail(SMPQ_E_INVALID, "smpq_pack_weights_grouped: wlimbs == 1 needs step and offset");
+  const int K = cg * kh * kw;
+  hipLaunchKernelGGL(pack_weights_ex_kernel, dim3(cout), dim3(kQThreads), 0, (hipStream_t)stream, w, cg, kh, kw, cg,
+                     K, wlimbs, 0, step, codes, (long long)cout * K, offset, wscale, status);
+  return check_hip(hipGetLastError(), "pack_weights_ex_kernel launch");
+}
+
 extern "C" int smpq_pack_weights_s2d_ex(const float* w, int cout, int cin, const float* step, int wlimbs,
                                         int8_t* codes, float* wscale, int32_t* status, smpq_stream_t stream) {
   if (!w || !codes || !wscale || !status || cout <= 0 || cin <= 0 || cin > 4)

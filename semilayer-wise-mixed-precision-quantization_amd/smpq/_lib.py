@@ -112,6 +112,12 @@ _PROTOS = {
     "smpq_u8lut_encode": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "smpq_u8lut_decode_host": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "smpq_u8lut_encode_host": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    "smpq_conv2d_grouped_supported": (_i, [_i] * 9),
+    "smpq_pack_weights_grouped": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "smpq_weights_grouped_expand_bytes": (ctypes.c_size_t, [_i] * 4),
+    "smpq_weights_grouped_expand": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "smpq_conv2d_grouped_fwd_q": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp,
+                                       _i, _i, _vp, _vp, _vp, ctypes.c_float, _vp, _vp]),
 }
 
 

@@ -163,9 +163,15 @@ class ResNet(nn.Module):
         return self.fc(torch.flatten(self.avgpool(x), 1))
 
     def forward(self, x):
-        if self.fused and x.is_cuda and not self.training and self.dilation == 1 and self.groups == 1:
+        if self.fused and x.is_cuda and not self.training and self.dilation == 1 and self._grouped_ok():
             return engine.forward_fused(self, x)
         return self._forward_impl(x)
+
+    def _grouped_ok(self):
+        """groups == 1, or every grouped conv of the model runs on the grouped HIP kernel."""
+        if self.groups == 1:
+            return True
+        return all(m.hip_supported() for m in self.modules() if isinstance(m, QConv2d) and m.groups != 1)
 
     def _apply(self, fn, *args, **kwargs):
         # .to() / .cuda() / .half() that replace parameter or buffer tensors: drop the engine's cached

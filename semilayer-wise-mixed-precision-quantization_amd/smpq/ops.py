@@ -766,6 +766,112 @@ def conv2d_q(xq, x_absmax, codes, offset, kh, kw, stride, pad, col_scale, col_sh
     return out
 
 
+# ---- grouped 3x3 conv (include/smpq.h: the conv2 of a ResNeXt Bottleneck) -------------------------
+# SMPQ_GROUPED=0 puts every grouped conv back on torch (QConv2d.hip_supported then refuses it)
+GROUPED = [os.environ.get("SMPQ_GROUPED", "1") != "0"]
+
+
+def conv_grouped_supported(cin, cout, groups, kh, kw, stride, pad, limbs=None, wlimbs=3):
+    """Does smpq_conv2d_grouped_fwd_q take this geometry (and is the SMPQ_GROUPED switch on)?"""
+    limbs = get_act_limbs() if limbs is None else limbs
+    return GROUPED[0] and bool(_lib.load().smpq_conv2d_grouped_supported(
+        int(cin), int(cout), int(groups), int(kh), int(kw), int(stride), int(pad), int(limbs), int(wlimbs)))
+
+
+def pack_weights_grouped(w, step, wlimbs, groups):
+    """Weight codes of a grouped 3x3 conv for conv2d_grouped_q: w fp32 [cout, cin / groups, 3, 3] ->
+    (codes int8 [wlimbs, cout, 9 * cin / groups], offset int32 [cout], wscale fp32 [cout], status int32
+    [3] (device)), the rows coded as pack_weights_ex codes them. The fragment-ordered block-diagonal
+    copy the kernel reads (smpq_weights_grouped_expand) is attached to ``codes`` and lives and dies
+    with them; ``codes._smpq_groups`` keeps ``groups``."""
+    _req(w.is_cuda and w.dtype == torch.float32 and w.dim() == 4, "pack_weights_grouped: need a CUDA fp32 4-D weight")
+    _req(wlimbs in (1, 3), "pack_weights_grouped: wlimbs must be 1 or 3")
+    w = w.contiguous()
+    cout, cg, kh, kw = w.shape
+    groups = int(groups)
+    _req(groups >= 2 and cout % groups == 0, "pack_weights_grouped: groups")
+    nbytes = int(_lib.load().smpq_weights_grouped_expand_bytes(int(wlimbs), cout, cg, groups)) if (kh, kw) == (3, 3) else 0
+    _req(nbytes > 0, "pack_weights_grouped: not a grouped 3x3 conv the kernel takes (conv_grouped_supported)")
+    if step is not None:
+        step = step.to(device=w.device, dtype=torch.float32).contiguous()
+        _req(step.numel() == cout, "pack_weights_grouped: step length")
+    _req(wlimbs >= 2 or step is not None, "pack_weights_grouped: wlimbs=1 needs step")
+    codes = torch.empty(wlimbs, cout, 9 * cg, dtype=torch.int8, device=w.device)
+    offset = torch.zeros(cout, dtype=torch.int32, device=w.device)
+    wscale = torch.empty(cout, dtype=torch.float32, device=w.device)
+    status = torch.zeros(3, dtype=torch.int32, device=w.device)
+    _launch(w.device, "smpq_pack_weights_grouped", w, cout, cg, kh, kw, step, int(wlimbs), codes, offset, wscale, status)
+    expanded = torch.empty(nbytes, dtype=torch.int8, device=w.device)
+    _launch(w.device, "smpq_weights_grouped_expand", codes, int(wlimbs), cout, cg, groups, expanded)
+    codes._smpq_gx = expanded
+    codes._smpq_groups = groups
+    return codes, offset, wscale, status
+
+
+def conv2d_grouped_q(xq, x_absmax, codes, offset, stride, col_scale, col_shift, relu=False, y_absmax=None, out=None,
+                     emit_range=None, overflow=None, want_f32=True):
+    """Grouped 3x3 / pad 1 conv on int8 limb planes xq [3, n, h, w, cin] with the codes of
+    pack_weights_grouped ([LW, cout, 9 * cin / groups], LW 1 or 3): y = conv(x, w) * s_x * col_scale +
+    col_shift (relu), NHWC fp32; with ``emit_range`` also (or, with want_f32=False, only) the output's
+    limb planes [3, n, ho, wo, cout], returned as (y or None, yq), with ``overflow`` set when a value
+    exceeded the range. No residual. A batch whose tensors would reach 2 GiB runs in image chunks."""
+    _req(xq.is_cuda and xq.dtype == torch.int8 and xq.dim() == 5 and xq.is_contiguous(),
+         "grouped conv: xq must be [L,n,h,w,c] int8")
+    limbs, n, h, w, cin = xq.shape
+    expanded, groups = getattr(codes, "_smpq_gx", None), getattr(codes, "_smpq_groups", None)
+    _req(expanded is not None and groups is not None and codes.dim() == 3, "grouped conv: codes of pack_weights_grouped")
+    wlimbs, cout, K = codes.shape
+    _req(cin % groups == 0 and K == 9 * (cin // groups) and codes.dtype == torch.int8 and codes.is_contiguous()
+         and codes.device == xq.device and expanded.device == xq.device, "grouped conv: codes shape")
+    _req(conv_grouped_supported(cin, cout, groups, 3, 3, stride, 1, limbs, wlimbs),
+         "grouped conv: unsupported geometry or limb counts (conv_grouped_supported)")
+    _req(offset is None or (offset.dtype == torch.int32 and offset.numel() == cout and wlimbs == 1),
+         "grouped conv: offset")
+    _req(x_absmax.dtype == torch.float32 and x_absmax.numel() == n, "grouped conv: x_absmax")
+    for t in (col_scale, col_shift):
+        _req(t.dtype == torch.float32 and t.numel() == cout and t.is_contiguous() and t.device == xq.device,
+             "grouped conv: col vectors")
+    ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+    yq = None
+    if emit_range is not None:
+        _req(emit_range > 0, "grouped conv: emit_range must be > 0")
+        _req(overflow is not None and overflow.dtype == torch.int32 and overflow.device == xq.device,
+             "grouped conv: overflow")
+        yq = torch.empty(limbs, n, ho, wo, cout, dtype=torch.int8, device=xq.device)
+    else:
+        want_f32 = True
+    if out is None and want_f32:
+        out = torch.empty(n, ho, wo, cout, dtype=torch.float32, device=xq.device)
+    _req(out is None or (out.shape == (n, ho, wo, cout) and out.is_contiguous()), "grouped conv: out shape")
+    if y_absmax is not None:
+        _req(y_absmax.numel() == n and y_absmax.dtype == torch.float32, "grouped conv: y_absmax")
+    # the kernel's 32-bit offsets run over all three limb planes of a tensor
+    per_img = max(limbs * h * w * cin, (limbs if yq is not None else 0) * ho * wo * cout,
+                  (4 if out is not None else 0) * ho * wo * cout)
+    chunks = _image_chunks(n, per_img, "grouped conv")
+    if chunks:
+        for i0, i1 in chunks:
+            r = conv2d_grouped_q(xq[:, i0:i1].contiguous(), x_absmax[i0:i1], codes, offset, stride, col_scale,
+                                 col_shift, relu=relu, y_absmax=None if y_absmax is None else y_absmax[i0:i1],
+                                 out=None if out is None else out[i0:i1], emit_range=emit_range, overflow=overflow,
+                                 want_f32=want_f32)
+            if yq is not None:
+                yq[:, i0:i1].copy_(r[1])
+        return (out, yq) if emit_range is not None else out
+    hook = _CONV_HOOK[0]
+    if hook is not None:
+        hook.begin()
+    _launch(xq.device, "smpq_conv2d_grouped_fwd_q", xq, x_absmax, n, h, w, cin, codes, expanded, int(wlimbs), offset,
+            cout, int(groups), 3, 3, int(stride), 1, col_scale, col_shift, 1 if relu else 0, int(limbs), out, y_absmax,
+            yq, float(emit_range or 0.0), overflow)
+    if hook is not None:
+        hook.end(alg_work(n, h, w, cin // groups, cout, 3, 3, ho, wo, limbs, wlimbs, out is not None, yq is not None,
+                          False, False))
+    if emit_range is not None:
+        return out, yq
+    return out
+
+
 def conv_pair_supported(cin, cout1, cout2, limbs=3):
     """Does smpq_conv2d_pair_fwd run this Bottleneck chain (conv3 cin -> cout1, next conv1 cout1 ->
     cout2)?"""

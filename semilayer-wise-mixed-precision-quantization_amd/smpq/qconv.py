@@ -16,8 +16,9 @@ Channels that were never quantized (bit 32 in the reference's bookkeeping: the s
 downsample convs, mid-search semilayers) have no integer code; they run on the same HIP kernel
 with their fp32 weights in per-channel fixed point with as many int8 limbs as the activations
 (16 or 24 bits), counted in ``smpq.stats["fixed_conv"]``. The 7x7/2/3 stem on <= 4 channels runs
-as a 4x4 conv over space-to-depth pixels on the same kernel. Only geometries the kernel does not
-cover (groups, dilation, other convs with cin % 64 != 0 or cout % 16 != 0) fall back to
+as a 4x4 conv over space-to-depth pixels on the same kernel. A grouped 3x3 conv (ResNeXt) runs on
+the block-diagonal kernel of csrc/conv_grouped.hip. Only geometries the kernels do not cover
+(other grouped convs, dilation, other convs with cin % 64 != 0 or cout % 16 != 0) fall back to
 ``F.conv2d`` on the GPU (counted in ``stats["fp32_conv"]``).
 """
 import weakref
@@ -149,10 +150,15 @@ class QConv2d(nn.Conv2d):
                 self.qstep._version, self.qbits._version, ops.get_act_limbs(), self._content_gen)
 
     def hip_supported(self):
-        return (self.weight.is_cuda and self.groups == 1 and self.dilation == (1, 1)
-                and self.padding_mode == "zeros" and self.stride[0] == self.stride[1]
-                and self.padding[0] == self.padding[1]
-                and self.in_channels % 64 == 0 and self.out_channels % 16 == 0)
+        ok = (self.weight.is_cuda and self.dilation == (1, 1)
+              and self.padding_mode == "zeros" and self.stride[0] == self.stride[1]
+              and self.padding[0] == self.padding[1])
+        if ok and self.groups != 1:
+            # the grouped 3x3 kernel (ops.conv2d_grouped_q): both weight forms packed() can produce
+            return all(ops.conv_grouped_supported(self.in_channels, self.out_channels, self.groups,
+                                                  self.kernel_size[0], self.kernel_size[1], self.stride[0],
+                                                  self.padding[0], wlimbs=lw) for lw in (1, 3))
+        return ok and self.in_channels % 64 == 0 and self.out_channels % 16 == 0
 
     def packed(self):
         """Weight operand of the HIP conv: (codes int8 [LW, cout, K], LW, offset | None,
@@ -170,9 +176,15 @@ class QConv2d(nn.Conv2d):
             return self._pack[1]
         res = None
         w = self.weight.detach()
+        if self.groups != 1:
+            # compact per-group codes + the kernel's block-diagonal copy (ops.pack_weights_grouped)
+            def pack(w, step, lw):
+                return ops.pack_weights_grouped(w, step, lw, self.groups)
+        else:
+            pack = ops.pack_weights_ex
         with torch.no_grad():
-            if self.fully_quantized() and self.in_channels % 64 == 0:
-                codes, offset, wscale, status = ops.pack_weights_ex(w, self.qstep, 1)
+            if self.fully_quantized() and (self.in_channels % 64 == 0 or self.groups != 1):
+                codes, offset, wscale, status = pack(w, self.qstep, 1)
                 st = status.cpu()
                 if int(st[0]) == 0 and int(st[1]) == 0:
                     has_off = bool((offset != 0).any().item())
@@ -180,7 +192,7 @@ class QConv2d(nn.Conv2d):
             if res is None:
                 step = self.qstep if (self._bits_host > 0).any() else None
                 lw = max(2, ops.get_act_limbs())
-                codes, _, wscale, status = ops.pack_weights_ex(w, step, lw)
+                codes, _, wscale, status = pack(w, step, lw)
                 kind = "fixed" if int(status.cpu()[2]) > 0 else "exact16"
                 res = (codes, lw, None, wscale, kind)
         stats["repack"] += 1
@@ -247,6 +259,9 @@ class QConv2d(nn.Conv2d):
         xq = ops.act_quantize(xh, amax)
         shift = self.bias.detach().float().contiguous() if self.bias is not None else \
             torch.zeros(self.out_channels, dtype=torch.float32, device=x.device)
-        y = ops.tuned_conv2d_q(xq, amax, codes, offset, self.kernel_size[0], self.kernel_size[1],
-                               self.stride[0], self.padding[0], wscale.contiguous(), shift)
+        if self.groups != 1:
+            y = ops.conv2d_grouped_q(xq, amax, codes, offset, self.stride[0], wscale.contiguous(), shift)
+        else:
+            y = ops.tuned_conv2d_q(xq, amax, codes, offset, self.kernel_size[0], self.kernel_size[1],
+                                   self.stride[0], self.padding[0], wscale.contiguous(), shift)
         return y.permute(0, 3, 1, 2)

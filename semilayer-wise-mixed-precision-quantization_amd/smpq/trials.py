@@ -66,8 +66,8 @@ def _operand(conv, bn):
     """What the three patchable predicates ask of the operand alone: the ConvPlan of a QConv2d whose
     codes are [LW, cout, K] with the K-major copy there exactly when ops.KMAJOR is on and K a multiple
     of 64 within the patch kernels' row limit; None otherwise."""
-    if not isinstance(conv, QConv2d):
-        return None
+    if not isinstance(conv, QConv2d) or conv.groups != 1:
+        return None  # (a grouped conv's kernel reads the expanded copy, which the row patches do not write)
     plan = engine.conv_plan(conv, bn)
     if plan is None or plan.codes.dim() != 3:
         return None
