@@ -257,6 +257,35 @@ int smpq_conv2d_chain_fwd(const int8_t* xq, const float* x_absmax, int n, int h,
                           const float* col_scale2, const float* col_shift2, int8_t* yq2, float yq2_range,
                           int32_t* overflow, smpq_stream_t stream);
 
+/* (appended; ABI 7) smpq_conv2d_chain_fwd with sg slab groups per workgroup: a workgroup of 4 sg
+ * waves holds sg adjacent slabs of conv3's output channels and stages each activation tile (and the
+ * fused downsample's input tile) once for all of them. sg = 1 is smpq_conv2d_chain_fwd; every sg gives
+ * bitwise the same outputs and overflow flag, only the time differs (a tile choice as tile_cfg is).
+ * Built (smpq_conv2d_chain_sg_supported; offsets: conv3 has weight offsets): sg = 2 for the strided
+ * fused downsamples, 256 -> 1024 / ds 512 / 2 and, without weight offsets, 128 -> 512 / ds 256 / 2;
+ * other calls with sg != 1 return SMPQ_E_INVALID.
+ * smpq_resident_sg_grid / smpq_resident_sg_map are host-side views of the launch order, exported so
+ * that it can be checked without a GPU (tests/test_resident_sg_host.py); they launch nothing and no
+ * caller needs them to run a conv. A launch with sg = 1 keeps the plain order (slab = block % slabs).
+ * smpq_resident_sg_grid: the workgroups such a launch starts for a budget of resident workgroups
+ * (CUs x workgroups per CU), ntiles pixel tiles and nsslabs = slabs / sg super-slabs: a multiple of
+ * nsslabs, at most ntiles for each. smpq_resident_sg_map: the (super-slab, first tile) of workgroup
+ * block of blocks (tiles first, first + blocks / nsslabs, ...): the super-slabs of one tile sit at
+ * block indices 8 apart (one XCD) wherever 8 tile walkers fill a round; every (super-slab, first tile)
+ * pair is some block's, exactly once. */
+int smpq_conv2d_chain_sg_supported(int cin, int cout1, int ds_cin, int ds_stride, int limbs, int offsets, int sg);
+long long smpq_resident_sg_grid(long long budget, long long ntiles, int nsslabs);
+int smpq_resident_sg_map(int block, int blocks, int nsslabs, int* sslab, int* tile0);
+int smpq_conv2d_chain_fwd_sg(const int8_t* xq, const float* x_absmax, int n, int h, int w, int cin,
+                             const int8_t* codes1, const int32_t* offset1, int cout1, const float* col_scale1,
+                             const float* col_shift1, const int8_t* residual_q, float residual_range,
+                             const int8_t* ds_xq, const float* ds_x_absmax, int ds_h, int ds_w, int ds_cin,
+                             int ds_stride, const int8_t* ds_codes, int ds_wlimbs,
+                             const float* ds_col_scale, const float* ds_col_shift, float ds_range, int8_t* yq1,
+                             float yq1_range, const float* y1_absmax, const int8_t* codes2, int cout2,
+                             const float* col_scale2, const float* col_shift2, int8_t* yq2, float yq2_range,
+                             int32_t* overflow, int sg, smpq_stream_t stream);
+
 /* codes [wlimbs][cout][K] (K % 64 == 0, 16-B aligned) -> out [wlimbs][K/64][cout][64], the K-major
  * copy smpq_conv2d_fwd_q_km reads. */
 int smpq_weights_kmajor(const int8_t* codes, int wlimbs, int cout, int K, int8_t* out, smpq_stream_t stream);

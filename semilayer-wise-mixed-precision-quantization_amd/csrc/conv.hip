@@ -646,7 +646,24 @@ extern "C" int smpq_conv2d_chain_ds_supported(int cin, int cout1, int ds_cin, in
   return resident_chain_ds_supported(cin, cout1, ds_cin, ds_stride, limbs) ? 1 : 0;
 }
 
-extern "C" int smpq_conv2d_chain_fwd(const int8_t* xq, const float* x_absmax, int n, int h, int w, int cin,
+extern "C" int smpq_conv2d_chain_sg_supported(int cin, int cout1, int ds_cin, int ds_stride, int limbs, int offsets,
+                                              int sg) {
+  return resident_chain_sg_supported(cin, cout1, ds_cin, ds_stride, limbs, offsets, sg) ? 1 : 0;
+}
+
+extern "C" long long smpq_resident_sg_grid(long long budget, long long ntiles, int nsslabs) {
+  if (budget < 0 || ntiles < 1 || nsslabs < 1) return fail(SMPQ_E_INVALID, "smpq_resident_sg_grid: bad arguments");
+  return resident_sg_grid(budget, ntiles, nsslabs);
+}
+
+extern "C" int smpq_resident_sg_map(int block, int blocks, int nsslabs, int* sslab, int* tile0) {
+  if (!sslab || !tile0 || nsslabs < 1 || blocks < nsslabs || blocks % nsslabs != 0 || block < 0 || block >= blocks)
+    return fail(SMPQ_E_INVALID, "smpq_resident_sg_map: bad arguments");
+  resident_sg_map(block, blocks, nsslabs, sslab, tile0);
+  return SMPQ_OK;
+}
+
+extern "C" int smpq_conv2d_chain_fwd_sg(const int8_t* xq, const float* x_absmax, int n, int h, int w, int cin,
                                      const int8_t* codes1, const int32_t* offset1, int cout1, const float* col_scale1,
                                      const float* col_shift1, const int8_t* residual_q, float residual_range,
                                      const int8_t* ds_xq, const float* ds_x_absmax, int ds_h, int ds_w,
@@ -655,8 +672,9 @@ extern "C" int smpq_conv2d_chain_fwd(const int8_t* xq, const float* x_absmax, in
                                      float ds_range, int8_t* yq1, float yq1_range, const float* y1_absmax,
                                      const int8_t* codes2, int cout2, const float* col_scale2,
                                      const float* col_shift2, int8_t* yq2, float yq2_range, int32_t* overflow,
-                                     smpq_stream_t stream) {
+                                     int sg, smpq_stream_t stream) {
   constexpr int limbs = 3;
+  // (the messages name smpq_conv2d_chain_fwd: its sg = 1 call of this function is the common one)
   if (!yq1 || (!residual_q) == (!ds_xq)) return fail(SMPQ_E_INVALID, "smpq_conv2d_chain_fwd: yq1 and exactly one "
                                                                       "identity source (residual_q or ds_xq)");
   if (ds_xq && (!ds_x_absmax || !ds_codes || ds_wlimbs != 3 || !(ds_range > 0.f)))
@@ -685,7 +703,24 @@ extern "C" int smpq_conv2d_chain_fwd(const int8_t* xq, const float* x_absmax, in
   long long big = (long long)limbs * a.M * (cout1 > cin ? cout1 : cin);
   if (ds_xq && (long long)limbs * d.plane > big) big = (long long)limbs * d.plane;
   if (big > 0x7fffff00LL) return fail(SMPQ_E_SHAPE, "smpq_conv2d_chain_fwd: a limb plane of 2 GiB or more");
-  return launch_resident_chain(a, codes2 ? &b : nullptr, ds_xq ? &d : nullptr, limbs, (hipStream_t)stream);
+  return launch_resident_chain(a, codes2 ? &b : nullptr, ds_xq ? &d : nullptr, limbs, sg, (hipStream_t)stream);
+}
+
+extern "C" int smpq_conv2d_chain_fwd(const int8_t* xq, const float* x_absmax, int n, int h, int w, int cin,
+                                     const int8_t* codes1, const int32_t* offset1, int cout1, const float* col_scale1,
+                                     const float* col_shift1, const int8_t* residual_q, float residual_range,
+                                     const int8_t* ds_xq, const float* ds_x_absmax, int ds_h, int ds_w,
+                                     int ds_cin, int ds_stride, const int8_t* ds_codes,
+                                     int ds_wlimbs, const float* ds_col_scale, const float* ds_col_shift,
+                                     float ds_range, int8_t* yq1, float yq1_range, const float* y1_absmax,
+                                     const int8_t* codes2, int cout2, const float* col_scale2,
+                                     const float* col_shift2, int8_t* yq2, float yq2_range, int32_t* overflow,
+                                     smpq_stream_t stream) {
+  return smpq_conv2d_chain_fwd_sg(xq, x_absmax, n, h, w, cin, codes1, offset1, cout1, col_scale1, col_shift1,
+                                  residual_q, residual_range, ds_xq, ds_x_absmax, ds_h, ds_w, ds_cin, ds_stride,
+                                  ds_codes, ds_wlimbs, ds_col_scale, ds_col_shift, ds_range, yq1, yq1_range,
+                                  y1_absmax, codes2, cout2, col_scale2, col_shift2, yq2, yq2_range, overflow, 1,
+                                  stream);
 }
 
 extern "C" int smpq_conv2d_pair_fwd(const int8_t* xq, const float* x_absmax, int n, int h, int w, int cin,

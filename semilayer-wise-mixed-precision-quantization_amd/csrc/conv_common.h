@@ -115,7 +115,12 @@ bool glds_is_resident_w(int cfg);
 // the Bottleneck tail chains: conv3 (+ fused downsample) (-> next conv1) (smpq_conv2d_chain_fwd)
 bool resident_pair_supported(int cin, int cout1, int cout2, int limbs);
 bool resident_chain_ds_supported(int cin, int cout1, int ds_cin, int ds_stride, int limbs);
-int launch_resident_chain(const ConvArgs& a, const ConvArgs* b, const ConvArgs* d, int limbs, hipStream_t s);
+// sg: slab groups per workgroup (1, or one resident_chain_sg_supported takes)
+bool resident_chain_sg_supported(int cin, int cout1, int ds_cin, int ds_stride, int limbs, int offsets, int sg);
+int launch_resident_chain(const ConvArgs& a, const ConvArgs* b, const ConvArgs* d, int limbs, int sg, hipStream_t s);
+// the grid and the block -> (super-slab, first tile) order of a launch with slab groups
+void resident_sg_map(int block, int blocks, int nss, int* sslab, int* tile0);
+long long resident_sg_grid(long long budget, long long ntiles, int nss);
 
 // The 4 codes (channels 0..3) held by one dword per limb plane, w[l] = the 4 balanced digits of
 // limb l: q = sum_l d_l 256^l. With u_l = d_l + 128 (byte ^ 0x80) for the low limbs,

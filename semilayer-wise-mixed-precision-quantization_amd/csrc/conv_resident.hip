@@ -40,6 +40,15 @@
 // own launch would have written) feed conv3's residual directly: both HBM round trips of the
 // downsample output and its launch disappear; the overflow flag covers both outputs.
 //
+// Slab groups (SG > 1; the strided fused-downsample chains of layers 2 and 3, whose 28 weight
+// fragments per wave force 128- and 64-channel slabs, 4 and 16 per conv): a workgroup of 4 SG waves
+// holds SG adjacent slabs, wave group g the slab SG sslab + g exactly as a 4-wave workgroup holds
+// one. The activation stages (and the downsample's input tile) are staged ONCE per workgroup, every
+// wave issuing its share of the DMA pieces, and read by all SG groups; only the staged output /
+// residual tiles and the copy-out are per group. The cout / (64 CW SG) super-slabs that still share
+// a tile are the workgroups b, b + 8, b + 16, ... (res_block_map): one XCD, one L2, adjacent in its
+// launch order. The per-channel arithmetic is untouched: bitwise the SG = 1 launch.
+//
 // Weight offsets (OFF; exact-code channels whose codes sit off-centre): acc_l += offset_c * (sum of
 // the pixel's limb-l digits), the digit sums taken with v_dot4 on the B fragments — the LDS-DMA
 // kernel's exact integer correction.
@@ -84,8 +93,36 @@ __device__ __forceinline__ int ach(int c, int r) {
   else return c ^ (r & 15);
 }
 
+// Block -> (super-slab, first tile) of a grid of blocks = per_slab * nss workgroups (SG > 1), per_slab
+// tile walkers (tile t0, t0 + per_slab, ...) for each of the nss super-slabs that share a pixel tile.
+// Blocks are dealt to the 8 XCDs round-robin (block b on XCD b % 8), so the walkers come in rounds
+// of 8: in round q, walker 8 q + x has its nss super-slabs at blocks 8 (q nss + s) + x, s = 0 .. nss -
+// 1: all on XCD x, adjacent in its launch order. The last per_slab % 8 walkers do not fill a round
+// and keep the plain order (super-slab = block % nss). A bijection for every per_slab, nss >= 1.
+__host__ __device__ inline void res_block_map(int b, int blocks, int nss, int* sslab, int* t0) {
+  const int per_slab = blocks / nss;
+  const int full = (per_slab / 8) * 8 * nss;  // blocks of the whole rounds
+  if (b < full) {
+    const int x = b % 8, q = b / 8;
+    *sslab = q % nss;
+    *t0 = (q / nss) * 8 + x;
+  } else {
+    *sslab = (b - full) % nss;
+    *t0 = (per_slab / 8) * 8 + (b - full) / nss;
+  }
+}
+
+// the grid of a launch: as many workgroups as fit the CUs at once (budget), a multiple of the nss
+// (super-)slabs (every one walks the tiles with the same stride), at most one per (slab, tile)
+inline long long res_grid(long long budget, long long ntiles, int nss) {
+  long long per_slab = budget / nss;
+  if (per_slab > ntiles) per_slab = ntiles;
+  if (per_slab < 1) per_slab = 1;
+  return per_slab * nss;
+}
+
 template <int L, int LW, int KC, int CW, int WP, bool RES, int CW2 = 0, int LWD = 0, bool OFF = false,
-          int KCD = KC>
+          int KCD = KC, int SG = 1>
 struct ResShape {
   static constexpr int SMIN = limb_smin(L, LW);
   static constexpr int NACC = limb_nacc(L, LW);
@@ -95,7 +132,8 @@ struct ResShape {
   static constexpr int ASTAGE = ATILE + ATILE_D;
   static constexpr int OTILE = L * BP * BN;  // output (and residual) tile bytes
   static constexpr int OTILE2 = L * BP * 64 * CW2;  // the chained conv's output tile
-  static constexpr int LDS = 2 * ASTAGE + (RES ? 3 : 1) * OTILE + OTILE2;
+  static constexpr int GTILES = (RES ? 3 : 1) * OTILE + OTILE2;  // a slab group's output / residual tiles
+  static constexpr int LDS = 2 * ASTAGE + SG * GTILES;
   // VGPRs: weights (+ the chained conv's) + accumulators + one chunk's B fragments + addressing /
   // epilogue (~40)
   // (+ the fused downsample's accumulators and epilogue constants; the offsets and digit sums: the
@@ -104,8 +142,11 @@ struct ResShape {
   static constexpr int REGS = 4 * (LW * KC * CW + CW * CW2 + LWD * KCD * CW + NACC * CW * WP + L * WP) + 40 +
                               (LWD > 0 ? 8 * CW + 4 * CW * WP + (CW2 > 0 ? 4 * NACC_D * CW * WP : 0) : 0) +
                               (OFF ? 8 * CW + L * WP : 0) + (CW2 > 0 ? 8 * CW2 + 4 * L * CW2 * WP : 0);
-  // workgroups per CU (1 wave per SIMD each; past 256 the accumulators move to AGPRs)
-  static constexpr int MINW_R = REGS <= 120 ? 4 : (REGS <= 152 ? 3 : (REGS <= 240 ? 2 : 1));
+  // workgroups per CU (SG waves per SIMD each; past 256 the accumulators move to AGPRs). SG = 2 needs
+  // REGS <= 240 (two waves per SIMD, 256 registers each) and SG = 4 REGS <= 120: beyond that MINW_R is 0
+  // and the launcher's static_assert refuses the instantiation. REGS is an estimate: the compiler's
+  // resource report (no scratch) decides
+  static constexpr int MINW_R = (REGS <= 120 ? 4 : (REGS <= 152 ? 3 : (REGS <= 240 ? 2 : 1))) / SG;
   // + the per-image input scales (x_absmax / QMAX) of each conv, staged once (kNTab images)
   static constexpr int NTABS = 1 + (LWD > 0 ? 1 : 0) + (CW2 > 0 ? 1 : 0);
   static constexpr int LDS_TOTAL = LDS + NTABS * kNTab * 4;
@@ -114,10 +155,10 @@ struct ResShape {
 };
 
 template <int L, int LW, int KC, int CW, int WP, bool RELU, bool RES, int MINW, int CW2 = 0, bool OFF = false,
-          int LWD = 0, int KCD = KC>
-__global__ __launch_bounds__(kResThreads, MINW) void qconv_resident_kernel(ConvArgs a, ConvArgs b, ConvArgs d,
-                                                                           int ntiles, int nslabs) {
-  using S = ResShape<L, LW, KC, CW, WP, RES, CW2, LWD, OFF, KCD>;
+          int LWD = 0, int KCD = KC, int SG = 1>
+__global__ __launch_bounds__(kResThreads * SG, MINW) void qconv_resident_kernel(ConvArgs a, ConvArgs b, ConvArgs d,
+                                                                                int ntiles, int nslabs) {
+  using S = ResShape<L, LW, KC, CW, WP, RES, CW2, LWD, OFF, KCD, SG>;
   constexpr int SMIN = S::SMIN, NACC = S::NACC, BN = S::BN, BP = S::BP, K = S::K, ASTAGE = S::ASTAGE;
   constexpr int ATILE = S::ATILE;
   static_assert(!OFF || (LW == 1 && SMIN == 0), "weight offsets: exact codes only");
@@ -127,27 +168,41 @@ __global__ __launch_bounds__(kResThreads, MINW) void qconv_resident_kernel(ConvA
   constexpr int RP = 1024 / K;     // activation rows per 1-KiB DMA piece
   constexpr int APIECES = L * BP / RP;
   constexpr float qmax = act_qmax<L>();
-  extern __shared__ __attribute__((aligned(1024))) int8_t lds[];  // 2 act stages, output tile, 2 residual tiles
+  // 2 act stages (shared), then per slab group: output tile, 2 residual tiles, the chained conv's tile
+  extern __shared__ __attribute__((aligned(1024))) int8_t lds[];
   const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wave_wg = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // of the workgroup: the DMA shares
+  const int sgi = SG > 1 ? wave_wg >> 2 : 0;                             // slab group
+  const int wave = SG > 1 ? wave_wg & 3 : wave_wg;                       // of the slab group
+  const int tid = SG > 1 ? lane + 64 * wave : (int)threadIdx.x;  // of the slab group: the copy-out shares
   const int frow = lane & 15, grp = lane >> 4;
   const unsigned lds0 = __builtin_amdgcn_readfirstlane(lds_addr(lds));
-  int8_t* const otile = lds + 2 * ASTAGE;
+  const int gtiles = 2 * ASTAGE + sgi * S::GTILES;
+  int8_t* const otile = lds + gtiles;
   constexpr int OTILE = S::OTILE;
-  const unsigned rtile0 = lds0 + 2 * ASTAGE + OTILE;  // residual tile of stage s at rtile0 + s OTILE
+  const unsigned rtile0 = lds0 + gtiles + OTILE;  // residual tile of stage s at rtile0 + s OTILE
   // per-image scales: [0] this conv's input, [1] the fused downsample's, [2] the chained conv's
   float* const rtab = reinterpret_cast<float*>(lds + S::LDS);
   const bool tab_ok = a.n <= kNTab;
   if (tab_ok) {
-    for (int i = threadIdx.x; i < a.n; i += kResThreads) {
+    for (int i = threadIdx.x; i < a.n; i += kResThreads * SG) {
       rtab[i] = a.x_absmax[i] * a.inv_qmax;
       if constexpr (LWD > 0) rtab[kNTab + i] = d.x_absmax[i] * d.inv_qmax;
       if constexpr (CW2 > 0) rtab[(S::NTABS - 1) * kNTab + i] = b.x_absmax[i] * b.inv_qmax;
     }
   }  // (visible to every wave after the tile loop's first barrier)
-  const int slab = blockIdx.x % nslabs;
+  int slab, t, tstride;
+  if constexpr (SG == 1) {
+    slab = blockIdx.x % nslabs;
+    t = blockIdx.x / nslabs;
+    tstride = gridDim.x / nslabs;
+  } else {
+    int sslab;
+    res_block_map((int)blockIdx.x, (int)gridDim.x, nslabs / SG, &sslab, &t);
+    slab = sslab * SG + sgi;
+    tstride = gridDim.x / (nslabs / SG);
+  }
   const int n0 = slab * BN;
-  const int tstride = gridDim.x / nslabs;
 
   // ---- the slab's weight limbs -> VGPRs once: A fragment (lw, kc, i) of lane (g, p) = the 16
   // bytes of K chunk 4 kc + g of output channel n0 + 16 (CW wave + i) + p
@@ -209,7 +264,7 @@ __global__ __launch_bounds__(kResThreads, MINW) void qconv_resident_kernel(ConvA
   constexpr int CHD = KD / 16, RPD = 1024 / KD, DPIECES = LWD > 0 ? L * BP / RPD : 0;
   const int prowd = lane / CHD, pphysd = lane % CHD;
   auto issue_acts = [&](int t, int stage) {
-    for (int p = wave; p < APIECES; p += 4) {
+    for (int p = wave_wg; p < APIECES; p += 4 * SG) {
       const int l = p / (BP / RP), r = (p % (BP / RP)) * RP + prow;  // tile row (pixel) of this lane
       const int m = t * BP + r;
       unsigned src = kOOB;
@@ -222,7 +277,7 @@ __global__ __launch_bounds__(kResThreads, MINW) void qconv_resident_kernel(ConvA
       dma16(lds0 + stage * ASTAGE + p * 1024, xrs, src, __builtin_amdgcn_readfirstlane((unsigned)((long long)l * a.plane)));
     }
     if constexpr (LWD > 0) {
-      for (int p = wave; p < DPIECES; p += 4) {
+      for (int p = wave_wg; p < DPIECES; p += 4 * SG) {
         const int l = p / (BP / RPD), r = (p % (BP / RPD)) * RPD + prowd;
         const int m = t * BP + r;
         unsigned src = kOOB;
@@ -254,7 +309,6 @@ __global__ __launch_bounds__(kResThreads, MINW) void qconv_resident_kernel(ConvA
       }
     }
   };
-  int t = blockIdx.x / nslabs;
   if (t < ntiles) {
     issue_acts(t, 0);
     issue_res(t, 0);
@@ -310,7 +364,7 @@ __global__ __launch_bounds__(kResThreads, MINW) void qconv_resident_kernel(ConvA
   }
   const long long oplane2 = CW2 > 0 ? (long long)a.M * BN2 : 0;
   const v4i qrs4b = make_rsrc(CW2 > 0 ? b.yq : nullptr, (long long)L * oplane2);
-  int8_t* const otile2 = lds + 2 * ASTAGE + (RES ? 3 : 1) * OTILE;
+  int8_t* const otile2 = otile + (RES ? 3 : 1) * OTILE;
   const bool nt = __builtin_amdgcn_readfirstlane(a.nt_store) != 0;
   float vmax = 0.f;
 
@@ -319,7 +373,7 @@ __global__ __launch_bounds__(kResThreads, MINW) void qconv_resident_kernel(ConvA
     constexpr int RC = BN / 16, ITEMS = L * BP * RC;
 #pragma unroll
     for (int k = 0; k < (ITEMS + kResThreads - 1) / kResThreads; ++k) {
-      const int it = threadIdx.x + kResThreads * k;
+      const int it = tid + kResThreads * k;
       if (ITEMS % kResThreads == 0 || it < ITEMS) {
         const int l = it / (BP * RC), rem = it - l * (BP * RC);
         const int rt = rem / RC, c = rem - rt * RC;
@@ -333,7 +387,7 @@ __global__ __launch_bounds__(kResThreads, MINW) void qconv_resident_kernel(ConvA
       constexpr int RC2 = BN2 / 16, ITEMS2 = L * BP * RC2;
 #pragma unroll
       for (int k = 0; k < (ITEMS2 + kResThreads - 1) / kResThreads; ++k) {
-        const int it = threadIdx.x + kResThreads * k;
+        const int it = tid + kResThreads * k;
         if (ITEMS2 % kResThreads == 0 || it < ITEMS2) {
           const int l = it / (BP * RC2), rem = it - l * (BP * RC2);
           const int rt = rem / RC2, c = rem - rt * RC2;
@@ -513,7 +567,7 @@ __global__ __launch_bounds__(kResThreads, MINW) void qconv_resident_kernel(ConvA
           unsigned rw[L];
 #pragma unroll
           for (int l = 0; l < L; ++l)
-            rw[l] = *reinterpret_cast<const unsigned*>(lds + 2 * ASTAGE + (1 + stage) * OTILE + l * BP * BN + rt * BN +
+            rw[l] = *reinterpret_cast<const unsigned*>(otile + (1 + stage) * OTILE + l * BP * BN + rt * BN +
                                                        16 * (cc ^ swze<BN>(frow)) + 4 * grp);
           decode4<L>(rw, rqv);
         }
@@ -659,11 +713,13 @@ int launch_res_l(int cfg, const ConvArgs& a, hipStream_t s) {
 // the Bottleneck tail chain: conv3 (one slab with all its output channels, 16-pixel tiles) with
 // its identity as limb planes (LWD == 0) or as the fused downsample (LWD == 3), optionally the next
 // block's conv1 (CW2 > 0), conv3's weight offsets or not
-template <int L, int KC, int CW, int CW2, bool OFF, int LWD, int KCD = KC>
+// (SG slab groups per workgroup: the kernel's header)
+template <int L, int KC, int CW, int CW2, bool OFF, int LWD, int KCD = KC, int SG = 1>
 int launch_chain_one(const ConvArgs& a, const ConvArgs& b, const ConvArgs& d, hipStream_t s) {
-  using S = ResShape<L, 1, KC, CW, 1, LWD == 0, CW2, LWD, OFF, KCD>;
-  static_assert(S::MINW >= 1, "LDS per CU");
-  auto k = qconv_resident_kernel<L, 1, KC, CW, 1, true, LWD == 0, S::MINW, CW2, OFF, LWD, KCD>;
+  using S = ResShape<L, 1, KC, CW, 1, LWD == 0, CW2, LWD, OFF, KCD, SG>;
+  static_assert(S::MINW >= 1, "LDS per CU, registers per SIMD");
+  static_assert(S::LDS_TOTAL <= 160 * 1024, "LDS per workgroup");
+  auto k = qconv_resident_kernel<L, 1, KC, CW, 1, true, LWD == 0, S::MINW, CW2, OFF, LWD, KCD, SG>;
   static const hipError_t attr = [&] {
     const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, S::LDS_TOTAL);
@@ -673,11 +729,9 @@ int launch_chain_one(const ConvArgs& a, const ConvArgs& b, const ConvArgs& d, hi
   if (attr != hipSuccess) return check_hip(attr, "qconv_resident_kernel (chain) LDS attribute");
   const long long ntiles = ((long long)a.M + S::BP - 1) / S::BP;
   const int nslabs = a.cout / S::BN;  // 1 with a chained conv (it needs every channel of the tile)
-  long long per_slab = (long long)device_cus_res() * S::MINW / nslabs;
-  if (per_slab > ntiles) per_slab = ntiles;
-  if (per_slab < 1) per_slab = 1;
-  hipLaunchKernelGGL(k, dim3((unsigned)(per_slab * nslabs)), dim3(kResThreads), S::LDS_TOTAL, s, a, b, d, (int)ntiles,
-                     nslabs);
+  if (nslabs % SG != 0) return fail(SMPQ_E_INVALID, "smpq_conv2d_chain_fwd: slab groups do not divide the slabs");
+  const long long blocks = res_grid((long long)device_cus_res() * S::MINW, ntiles, nslabs / SG);
+  hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(kResThreads * SG), S::LDS_TOTAL, s, a, b, d, (int)ntiles, nslabs);
   return check_hip(hipGetLastError(), "qconv_resident_kernel (chain) launch");
 }
 
@@ -774,7 +828,20 @@ bool resident_chain_ds_supported(int cin, int cout1, int ds_cin, int ds_stride, 
                         (cin == 256 && cout1 == 1024 && ds_cin == 512 && ds_stride == 2));
 }
 
-int launch_resident_chain(const ConvArgs& a, const ConvArgs* b, const ConvArgs* d, int limbs, hipStream_t s) {
+// the slab groups built for a fused-downsample chain: 2 for the strided ones (layers 2 and 3: 4 and
+// 16 slabs). Not 4: a wave's 28 weight fragments alone are 112 of the 128 registers that 16 waves
+// per CU leave it (ResShape::MINW_R: no workgroup fits). Not layer 2's with weight offsets: its
+// one-group kernel already takes all 256 registers, and two groups spill (12 bytes of scratch per lane)
+bool resident_chain_sg_supported(int cin, int cout1, int ds_cin, int ds_stride, int limbs, int offsets, int sg) {
+  return resident_chain_ds_supported(cin, cout1, ds_cin, ds_stride, limbs) &&
+         (sg == 1 || (sg == 2 && ds_stride == 2 && !(cin == 128 && offsets)));
+}
+
+void resident_sg_map(int block, int blocks, int nss, int* sslab, int* tile0) { res_block_map(block, blocks, nss, sslab, tile0); }
+
+long long resident_sg_grid(long long budget, long long ntiles, int nss) { return res_grid(budget, ntiles, nss); }
+
+int launch_resident_chain(const ConvArgs& a, const ConvArgs* b, const ConvArgs* d, int limbs, int sg, hipStream_t s) {
   auto conv1x1 = [](const ConvArgs& c) { return c.kh == 1 && c.kw == 1 && c.stride == 1 && c.pad == 0 && !c.s2d; };
   auto ds1x1 = [](const ConvArgs& c) { return c.kh == 1 && c.kw == 1 && c.pad == 0 && !c.s2d; };
   const bool shapes_ok =
@@ -796,12 +863,17 @@ int launch_resident_chain(const ConvArgs& a, const ConvArgs* b, const ConvArgs* 
   const ConvArgs& bb = b ? *b : a;
   const ConvArgs& dd = d ? *d : a;
   const bool off = a.has_offset != 0;
+  if (sg != 1 && !(d && !b && resident_chain_sg_supported(a.cin, a.cout, d->cin, d->stride, limbs, off, sg)))
+    return fail(SMPQ_E_INVALID, "smpq_conv2d_chain_fwd_sg: this many slab groups are not built for this chain "
+                                "(smpq_conv2d_chain_sg_supported)");
   if (d) {
     // conv3 + the fused downsample: 128-channel slabs (three workgroups per CU). With the chained
     // conv1 as well it needs one 256-channel slab, ~410 registers per lane and one workgroup per
     // CU: measured 4-5 % slower on the R50 step than without (profiles/r06_chain_fused_ds.txt); not built
     if (b) return fail(SMPQ_E_INVALID, "smpq_conv2d_chain_fwd: the fused downsample is built without a chained conv1");
     // (layer2 / layer3: 128- / 64-channel slabs, the downsample's K 256 / 512 beside conv3's 128 / 256)
+    if (a.cin == 128 && sg == 2) return launch_chain_one<3, 2, 2, 0, false, 3, 4, 2>(a, bb, dd, s);
+    if (a.cin == 256 && sg == 2) return off ? launch_chain_one<3, 4, 1, 0, true, 3, 8, 2>(a, bb, dd, s) : launch_chain_one<3, 4, 1, 0, false, 3, 8, 2>(a, bb, dd, s);
     if (a.cin == 128) return off ? launch_chain_one<3, 2, 2, 0, true, 3, 4>(a, bb, dd, s) : launch_chain_one<3, 2, 2, 0, false, 3, 4>(a, bb, dd, s);
     if (a.cin == 256) return off ? launch_chain_one<3, 4, 1, 0, true, 3, 8>(a, bb, dd, s) : launch_chain_one<3, 4, 1, 0, false, 3, 8>(a, bb, dd, s);
     return off ? launch_chain_one<3, 1, 2, 0, true, 3>(a, bb, dd, s) : launch_chain_one<3, 1, 2, 0, false, 3>(a, bb, dd, s);

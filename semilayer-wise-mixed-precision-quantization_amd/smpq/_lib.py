@@ -61,6 +61,13 @@ _PROTOS = {
                                    _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, ctypes.c_float, _vp,
                                    ctypes.c_float, _vp,
                                    _vp, _i, _vp, _vp, _vp, ctypes.c_float, _vp, _vp]),
+    "smpq_conv2d_chain_sg_supported": (_i, [_i] * 7),
+    "smpq_resident_sg_grid": (ctypes.c_longlong, [ctypes.c_longlong, ctypes.c_longlong, _i]),
+    "smpq_resident_sg_map": (_i, [_i, _i, _i, _vp, _vp]),
+    "smpq_conv2d_chain_fwd_sg": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, ctypes.c_float,
+                                      _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, ctypes.c_float, _vp,
+                                      ctypes.c_float, _vp,
+                                      _vp, _i, _vp, _vp, _vp, ctypes.c_float, _vp, _i, _vp]),
     "smpq_conv2d_pair_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, ctypes.c_float, _vp,
                                   ctypes.c_float, _vp, _vp, _i, _vp, _vp, _vp, ctypes.c_float, _vp, _vp]),
     "smpq_maxpool_limbs": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),

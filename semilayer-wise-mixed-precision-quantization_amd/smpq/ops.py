@@ -891,6 +891,33 @@ def conv_chain_ds_supported(cin, cout1, ds_cin, ds_stride, limbs=3):
                                                            int(limbs)))
 
 
+def conv_chain_sg_supported(cin, cout1, ds_cin, ds_stride, offsets, sg, limbs=3):
+    """Does smpq_conv2d_chain_fwd_sg run this fused-downsample chain (``offsets``: conv3 has weight
+    offsets) with ``sg`` slab groups per workgroup?"""
+    return bool(_lib.load().smpq_conv2d_chain_sg_supported(int(cin), int(cout1), int(ds_cin), int(ds_stride),
+                                                          int(limbs), 1 if offsets else 0, int(sg)))
+
+
+def chain_sg_key(n, h, w, cin, cout1, ds_cin, ds_stride, offsets):
+    """The tile table's key of a fused-downsample chain launch; its entry is the launch's slab groups."""
+    return ("chain", n, h, w, cin, cout1, ds_cin, ds_stride, bool(offsets))
+
+
+def _chain_sg(n, h, w, cin, cout1, ds_cin, ds_stride, offsets):
+    """The slab groups of a fused-downsample chain launch: the committed table's entry where that is
+    built (a shape the table does not list runs with one group, the launch of smpq_conv2d_chain_fwd)."""
+    if not _TABLE.get("loaded"):
+        load_tile_table()
+    ks = key_str(chain_sg_key(n, h, w, cin, cout1, ds_cin, ds_stride, offsets))
+    sg = _TABLE["entries"].get(ks, 1)
+    if sg == 1 or not conv_chain_sg_supported(cin, cout1, ds_cin, ds_stride, offsets, sg):
+        return 1
+    if ks not in _TABLE["chain_hits"]:  # a table hit, counted once per shape as _choose_tile's are
+        _TABLE["chain_hits"].add(ks)
+        _TABLE["hits"] += 1
+    return sg
+
+
 def _one_limb(codes, what):
     _req(codes.dim() == 2 or codes.shape[0] == 1, "chain: %s needs exact codes (one weight limb)" % what)
     return codes[0] if codes.dim() == 3 else codes
@@ -904,7 +931,7 @@ ChainNext = namedtuple("ChainNext", "codes col_scale col_shift rng")
 
 
 def conv_chain_q(xq, x_absmax, codes1, offset1, col_scale1, col_shift1, emit_range1, y1_absmax, overflow,
-                 residual_q=None, residual_range=None, ds=None, nxt=None):
+                 residual_q=None, residual_range=None, ds=None, nxt=None, sg=None):
     """A Bottleneck's conv3 (1x1 + folded BN + identity + ReLU, exact codes, optional weight offsets)
     in one launch with (csrc/conv_resident.hip, smpq_conv2d_chain_fwd):
       - its identity: ``residual_q`` limb planes (+ ``residual_range``), or ``ds`` (a ChainDs, or its
@@ -912,6 +939,8 @@ def conv_chain_q(xq, x_absmax, codes1, offset1, col_scale1, col_shift1, emit_ran
         output pixels, computed in the same tiles (its output codes feed the residual; never written);
       - ``nxt`` (a ChainNext, or its fields as a plain tuple): the next block's conv1 (ReLU) on
         conv3's output tile.
+    ``sg``: the slab groups per workgroup of a fused-downsample launch (conv_chain_sg_supported; None:
+    the tile table's choice for the shape, 1 where it has none). Every ``sg`` gives the same bits.
     Returns (yq1, yq2 or None), bitwise what the separate launches write; ``overflow`` covers every
     output of the chain (the downsample's included)."""
     ds = None if ds is None else ChainDs(*ds)
@@ -966,7 +995,7 @@ def conv_chain_q(xq, x_absmax, codes1, offset1, col_scale1, col_shift1, emit_ran
                 residual_q=None if residual_q is None else residual_q[:, i0:i1].contiguous(),
                 residual_range=residual_range,
                 ds=None if ds is None else ds._replace(xq=dxq[:, i0:i1].contiguous(), x_absmax=ds.x_absmax[i0:i1]),
-                nxt=nxt)
+                nxt=nxt, sg=sg)
             yq1[:, i0:i1].copy_(a)
             if b is not None:
                 yq2[:, i0:i1].copy_(b)
@@ -977,11 +1006,15 @@ def conv_chain_q(xq, x_absmax, codes1, offset1, col_scale1, col_shift1, emit_ran
     # (an absent downsample / next conv: null pointers and zeros)
     d = ds or ChainDs(None, None, None, None, None, 0.0, 0)
     nx = nxt or ChainNext(None, None, None, 0.0)
-    _launch(xq.device, "smpq_conv2d_chain_fwd", xq, x_absmax, n, h, w, cin, c1, offset1, cout1, col_scale1, col_shift1,
+    if sg is None:
+        sg = _chain_sg(n, h, w, cin, cout1, dcin, int(ds.stride), offset1 is not None) if ds is not None else 1
+    _req(sg == 1 or (ds is not None and conv_chain_sg_supported(cin, cout1, dcin, int(ds.stride), offset1 is not None,
+                                                                 sg)), "chain: slab groups not built")
+    _launch(xq.device, "smpq_conv2d_chain_fwd_sg", xq, x_absmax, n, h, w, cin, c1, offset1, cout1, col_scale1, col_shift1,
             residual_q, float(residual_range or 0.0),
             d.xq, d.x_absmax, dh, dw, dcin, int(d.stride), d.codes, 3 if ds else 0, d.col_scale, d.col_shift,
             float(d.rng), yq1, float(emit_range1), y1_absmax,
-            c2, cout2, nx.col_scale, nx.col_shift, yq2, float(nx.rng), overflow)
+            c2, cout2, nx.col_scale, nx.col_shift, yq2, float(nx.rng), overflow, int(sg))
     if hook is not None:
         # one launch doing every chained conv's work; the reads / writes it removes are not counted
         w1 = alg_work(n, h, w, cin, cout1, 1, 1, h, w, limbs, 1, False, True, False, residual_q is not None)
@@ -1042,7 +1075,7 @@ TUNE_CONCURRENT = [1]
 TUNE_LOG = {}
 _TUNED = {}
 TILE_TABLE_DEFAULT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", "tiles_gfx950.json")
-_TABLE = {"path": None, "sha16": None, "entries": {}, "hits": 0, "tuned": 0}
+_TABLE = {"path": None, "sha16": None, "entries": {}, "hits": 0, "tuned": 0, "chain_hits": set()}
 
 
 def key_str(key):
@@ -1059,7 +1092,7 @@ def load_tile_table(path=None):
     import hashlib
     import json
     path = path or os.environ.get("SMPQ_TILE_TABLE", TILE_TABLE_DEFAULT)
-    _TABLE.update(path=None, sha16=None, entries={}, hits=0, tuned=0, loaded=True)
+    _TABLE.update(path=None, sha16=None, entries={}, hits=0, tuned=0, loaded=True, chain_hits=set())
     if path in ("off", "0", "") or not os.path.exists(path):
         return _TABLE
     raw = open(path, "rb").read()

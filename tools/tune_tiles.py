@@ -40,6 +40,16 @@ def table_entries(ops):
     return dict(sorted(tiles.items()))
 
 
+def chain_entries(path):
+    """The chain|... entries of the table at ``path`` (the slab groups of the fused-downsample chain
+    launches, ops.chain_sg_key). They are set from an in-graph A/B of bench.py, not from timed single
+    launches (profiles/resident_sg_ab.txt), so a regenerated table carries them over unchanged."""
+    if not os.path.exists(path):
+        return {}
+    with open(path) as f:
+        return {k: int(v) for k, v in json.load(f).get("tiles", {}).items() if k.startswith("chain|")}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=25)
@@ -77,11 +87,12 @@ def main():
            "arch": getattr(torch.cuda.get_device_properties(0), "gcnArchName", "gfx950"),
            "made": datetime.datetime.utcnow().strftime("%Y-%m-%d %H:%M UTC"),
            "method": "tools/tune_tiles.py: median of %d timed launches per candidate (after 2 warm-ups)%s, "
-                     "workloads %s" % (args.reps, "" if args.concurrent == 1 else
+                     "workloads %s; chain|... entries carried over from the table this one replaces" % (args.reps, "" if args.concurrent == 1 else
                                        ", each launch %d copies on their own streams" % args.concurrent, args.configs),
            "key": "tuned_conv2d_q: n|h|w|cin|cout|kh|kw|stride|pad|limbs|wlimbs|res_f32|emit_q|want_f32|res_q; "
-                  "tuned_stem_conv_s2d: stem_s2d|planes|codes|h|w|y_absmax|emit_q|want_f32",
-           "tiles": table_entries(ops)}
+                  "tuned_stem_conv_s2d: stem_s2d|planes|codes|h|w|y_absmax|emit_q|want_f32; conv_chain_q with a "
+                  "fused downsample: chain|n|h|w|cin|cout1|ds_cin|ds_stride|offsets (the value is its slab groups)",
+           "tiles": dict(sorted({**table_entries(ops), **chain_entries(out)}.items()))}
     with open(out, "w") as f:
         json.dump(doc, f, indent=1, sort_keys=False)
         f.write("\n")
