@@ -778,6 +778,29 @@ int smpq_conv2d_grouped_fwd_q(const int8_t* xq, const float* x_absmax, int n, in
                               const float* col_shift, int relu, int limbs, float* y, float* y_absmax, int8_t* yq,
                               float yq_range, int32_t* overflow, smpq_stream_t stream);
 
+/* ---- dilated 3x3 conv (additions to ABI 7) -------------------------------------------------------
+ * The conv2 of a Bottleneck built with replace_stride_with_dilation (resnet.py conv3x3, dilation > 1):
+ * dense (groups 1), 3x3, stride 1, padding == dilation == d. Output pixel (ph + d i, pw + d j) reads
+ * only input pixels of its own phase (ph, pw), so the conv is d * d ordinary 3x3 / pad 1 convs on the
+ * phase lattices; the kernel (csrc/conv_dilated.hip) runs 8 x 8 lattice tiles of them.
+ * smpq_conv2d_dilated_supported: 1 exactly for 3x3, stride 1, pad == dilation in {2, 4, 8},
+ *   cin % 64 == 0, cout % 64 == 0, limbs == 3, wlimbs 1 or 3; else 0.
+ * smpq_conv2d_dilated_fwd_q: smpq_conv2d_fwd_q_km without a residual and without a tile choice, with
+ *   the dilation: y = relu?(conv_real * col_scale[c] + col_shift[c]) as fp32 NHWC y and / or limb
+ *   planes yq at the static yq_range with the overflow flag; y_absmax optional. codes are the dense
+ *   pack of smpq_pack_weights_ex, [wlimbs][cout][9 cin]; codes_kmajor their smpq_weights_kmajor copy,
+ *   which the kernel reads instead when it is not NULL (same results). All three activation planes
+ *   together, and each output tensor, stay below 2 GiB (SMPQ_E_SHAPE otherwise: split the batch).
+ *   SMPQ_E_SHAPE for a geometry smpq_conv2d_dilated_supported refuses, SMPQ_E_INVALID for null or
+ *   misaligned (16 B) pointers or other limb counts, before any launch. */
+int smpq_conv2d_dilated_supported(int cin, int cout, int kh, int kw, int stride, int pad, int dilation, int limbs,
+                                  int wlimbs);
+int smpq_conv2d_dilated_fwd_q(const int8_t* xq, const float* x_absmax, int n, int h, int w, int cin,
+                              const int8_t* codes, const int8_t* codes_kmajor, int wlimbs, const int32_t* offset,
+                              int cout, int kh, int kw, int stride, int pad, int dilation, const float* col_scale,
+                              const float* col_shift, int relu, int limbs, float* y, float* y_absmax, int8_t* yq,
+                              float yq_range, int32_t* overflow, smpq_stream_t stream);
+
 /* Diagnostics: one v_mfma_i32_16x16x64_i8 with the kernel's fragment mapping.
  *   a [16][64] int8 row-major, b [16][64] int8 (b[col][k]), c [16][16] int32 row-major */
 int smpq_debug_mfma_i8(const int8_t* a, const int8_t* b, int32_t* c, smpq_stream_t stream);

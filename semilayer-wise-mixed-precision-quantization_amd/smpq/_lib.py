@@ -125,6 +125,9 @@ _PROTOS = {
     "smpq_weights_grouped_expand": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "smpq_conv2d_grouped_fwd_q": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp,
                                        _i, _i, _vp, _vp, _vp, ctypes.c_float, _vp, _vp]),
+    "smpq_conv2d_dilated_supported": (_i, [_i] * 9),
+    "smpq_conv2d_dilated_fwd_q": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp,
+                                       _i, _i, _vp, _vp, _vp, ctypes.c_float, _vp, _vp]),
 }
 
 

@@ -41,6 +41,7 @@ content fingerprints of the conv weights / metadata / BN tensors (smpq/fingerpri
 after every forward: a write through ``.data`` (no version bump) is detected, the result is
 discarded and recomputed from freshly packed weights.
 """
+import functools
 import threading
 from collections import namedtuple
 
@@ -230,20 +231,25 @@ def run_conv(conv, bn, act, relu, residual=None, want_amax=True, ctx=None, want_
         conv.last_path = "hip-" + kind
         args = (act.limbs(), act.amax, codes, offset, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0],
                 conv.padding[0], col_scale, col_shift)
-        if conv.groups != 1:  # the grouped 3x3 kernel (a ResNeXt conv2: never the conv that adds the identity)
-            if residual is not None or res_q is not None:
-                raise RuntimeError("smpq: residual on a grouped conv")
-            gargs = (act.limbs(), act.amax, codes, offset, conv.stride[0], col_scale, col_shift)
+        special = None  # the grouped / dilated 3x3 kernels (a Bottleneck conv2: never the conv that adds the identity)
+        if conv.groups != 1:
+            special = functools.partial(ops.conv2d_grouped_q, act.limbs(), act.amax, codes, offset, conv.stride[0],
+                                        col_scale, col_shift)
+        elif conv.dilation[0] != 1:
+            special = functools.partial(ops.conv2d_dilated_q, act.limbs(), act.amax, codes, offset, conv.dilation[0],
+                                        col_scale, col_shift)
+        if special is not None and (residual is not None or res_q is not None):
+            raise RuntimeError("smpq: residual on a grouped or dilated conv")
         if static:
             rng = ctx.ranges[id(conv)]
-            if conv.groups != 1:
-                y, yq = ops.conv2d_grouped_q(*gargs, relu=relu, emit_range=rng, overflow=ctx.overflow, want_f32=want_f32)
+            if special is not None:
+                y, yq = special(relu=relu, emit_range=rng, overflow=ctx.overflow, want_f32=want_f32)
             else:
                 y, yq = ops.tuned_conv2d_q(*args, residual=residual, relu=relu, emit_range=rng, overflow=ctx.overflow,
                                            want_f32=want_f32, residual_q=res_q, residual_range=res_rng)
             return Act(f32=y, q=yq, amax=ctx.range_tensor(conv), rng=rng)
-        if conv.groups != 1:
-            y = ops.conv2d_grouped_q(*gargs, relu=relu, y_absmax=yam)
+        if special is not None:
+            y = special(relu=relu, y_absmax=yam)
         else:
             y = ops.tuned_conv2d_q(*args, residual=residual, relu=relu, y_absmax=yam, residual_q=res_q,
                                    residual_range=res_rng)

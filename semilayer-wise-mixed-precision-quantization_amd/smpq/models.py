@@ -163,9 +163,15 @@ class ResNet(nn.Module):
         return self.fc(torch.flatten(self.avgpool(x), 1))
 
     def forward(self, x):
-        if self.fused and x.is_cuda and not self.training and self.dilation == 1 and self._grouped_ok():
+        if self.fused and x.is_cuda and not self.training and self._dilated_ok() and self._grouped_ok():
             return engine.forward_fused(self, x)
         return self._forward_impl(x)
+
+    def _dilated_ok(self):
+        """No dilation, or every dilated conv of the model runs on the dilated HIP kernel."""
+        if self.dilation == 1:
+            return True
+        return all(m.hip_supported() for m in self.modules() if isinstance(m, QConv2d) and m.dilation != (1, 1))
 
     def _grouped_ok(self):
         """groups == 1, or every grouped conv of the model runs on the grouped HIP kernel."""

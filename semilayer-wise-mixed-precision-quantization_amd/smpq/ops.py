@@ -872,6 +872,82 @@ def conv2d_grouped_q(xq, x_absmax, codes, offset, stride, col_scale, col_shift, 
     return out
 
 
+# ---- dilated 3x3 conv (include/smpq.h: the conv2 of a Bottleneck with replace_stride_with_dilation) --
+# SMPQ_DILATED=0 puts every dilated conv back on torch (QConv2d.hip_supported then refuses it)
+DILATED = [os.environ.get("SMPQ_DILATED", "1") != "0"]
+
+
+def conv_dilated_supported(cin, cout, kh, kw, stride, pad, dilation, limbs=None, wlimbs=3):
+    """Does smpq_conv2d_dilated_fwd_q take this geometry (and is the SMPQ_DILATED switch on)?"""
+    limbs = get_act_limbs() if limbs is None else limbs
+    return DILATED[0] and bool(_lib.load().smpq_conv2d_dilated_supported(
+        int(cin), int(cout), int(kh), int(kw), int(stride), int(pad), int(dilation), int(limbs), int(wlimbs)))
+
+
+def conv2d_dilated_q(xq, x_absmax, codes, offset, dilation, col_scale, col_shift, relu=False, y_absmax=None, out=None,
+                     emit_range=None, overflow=None, want_f32=True):
+    """Dense 3x3 / stride 1 conv with padding = dilation (2, 4 or 8) on int8 limb planes xq
+    [3, n, h, w, cin] with the codes of pack_weights_ex ([LW, cout, 9 * cin], LW 1 or 3; their K-major
+    copy is read when it is attached and KMAJOR is on): y = conv(x, w) * s_x * col_scale + col_shift
+    (relu), NHWC fp32; with ``emit_range`` also (or, with want_f32=False, only) the output's limb planes
+    [3, n, h, w, cout], returned as (y or None, yq), with ``overflow`` set when a value exceeded the
+    range. No residual. A batch whose tensors would reach 2 GiB runs in image chunks."""
+    _req(xq.is_cuda and xq.dtype == torch.int8 and xq.dim() == 5 and xq.is_contiguous(),
+         "dilated conv: xq must be [L,n,h,w,c] int8")
+    limbs, n, h, w, cin = xq.shape
+    km = getattr(codes, "_smpq_km", None) if KMAJOR[0] else None
+    _req(codes.dim() == 3, "dilated conv: codes of pack_weights_ex")
+    wlimbs, cout, K = codes.shape
+    _req(K == 9 * cin and codes.dtype == torch.int8 and codes.is_contiguous() and codes.device == xq.device,
+         "dilated conv: codes shape")
+    _req(conv_dilated_supported(cin, cout, 3, 3, 1, dilation, dilation, limbs, wlimbs),
+         "dilated conv: unsupported geometry or limb counts (conv_dilated_supported)")
+    _req(km is None or (km.shape == (wlimbs, K // 64, cout, 64) and km.device == xq.device), "dilated conv: K-major codes")
+    _req(offset is None or (offset.dtype == torch.int32 and offset.numel() == cout and wlimbs == 1),
+         "dilated conv: offset")
+    _req(x_absmax.dtype == torch.float32 and x_absmax.numel() == n, "dilated conv: x_absmax")
+    for t in (col_scale, col_shift):
+        _req(t.dtype == torch.float32 and t.numel() == cout and t.is_contiguous() and t.device == xq.device,
+             "dilated conv: col vectors")
+    yq = None
+    if emit_range is not None:
+        _req(emit_range > 0, "dilated conv: emit_range must be > 0")
+        _req(overflow is not None and overflow.dtype == torch.int32 and overflow.device == xq.device,
+             "dilated conv: overflow")
+        yq = torch.empty(limbs, n, h, w, cout, dtype=torch.int8, device=xq.device)
+    else:
+        want_f32 = True
+    if out is None and want_f32:
+        out = torch.empty(n, h, w, cout, dtype=torch.float32, device=xq.device)
+    _req(out is None or (out.shape == (n, h, w, cout) and out.is_contiguous()), "dilated conv: out shape")
+    if y_absmax is not None:
+        _req(y_absmax.numel() == n and y_absmax.dtype == torch.float32, "dilated conv: y_absmax")
+    # the kernel's 32-bit offsets run over all three limb planes of a tensor
+    per_img = max(limbs * h * w * cin, (limbs if yq is not None else 0) * h * w * cout,
+                  (4 if out is not None else 0) * h * w * cout)
+    chunks = _image_chunks(n, per_img, "dilated conv")
+    if chunks:
+        for i0, i1 in chunks:
+            r = conv2d_dilated_q(xq[:, i0:i1].contiguous(), x_absmax[i0:i1], codes, offset, dilation, col_scale,
+                                 col_shift, relu=relu, y_absmax=None if y_absmax is None else y_absmax[i0:i1],
+                                 out=None if out is None else out[i0:i1], emit_range=emit_range, overflow=overflow,
+                                 want_f32=want_f32)
+            if yq is not None:
+                yq[:, i0:i1].copy_(r[1])
+        return (out, yq) if emit_range is not None else out
+    hook = _CONV_HOOK[0]
+    if hook is not None:
+        hook.begin()
+    _launch(xq.device, "smpq_conv2d_dilated_fwd_q", xq, x_absmax, n, h, w, cin, codes, km, int(wlimbs), offset, cout,
+            3, 3, 1, int(dilation), int(dilation), col_scale, col_shift, 1 if relu else 0, int(limbs), out, y_absmax,
+            yq, float(emit_range or 0.0), overflow)
+    if hook is not None:
+        hook.end(alg_work(n, h, w, cin, cout, 3, 3, h, w, limbs, wlimbs, out is not None, yq is not None, False, False))
+    if emit_range is not None:
+        return out, yq
+    return out
+
+
 def conv_pair_supported(cin, cout1, cout2, limbs=3):
     """Does smpq_conv2d_pair_fwd run this Bottleneck chain (conv3 cin -> cout1, next conv1 cout1 ->
     cout2)?"""

@@ -17,8 +17,10 @@ downsample convs, mid-search semilayers) have no integer code; they run on the s
 with their fp32 weights in per-channel fixed point with as many int8 limbs as the activations
 (16 or 24 bits), counted in ``smpq.stats["fixed_conv"]``. The 7x7/2/3 stem on <= 4 channels runs
 as a 4x4 conv over space-to-depth pixels on the same kernel. A grouped 3x3 conv (ResNeXt) runs on
-the block-diagonal kernel of csrc/conv_grouped.hip. Only geometries the kernels do not cover
-(other grouped convs, dilation, other convs with cin % 64 != 0 or cout % 16 != 0) fall back to
+the block-diagonal kernel of csrc/conv_grouped.hip, a dense 3x3 conv with padding = dilation 2, 4 or
+8 (replace_stride_with_dilation) on the phase-lattice kernel of csrc/conv_dilated.hip. Only geometries
+the kernels do not cover (other grouped convs, other dilations, grouped + dilated, other convs with
+cin % 64 != 0 or cout % 16 != 0) fall back to
 ``F.conv2d`` on the GPU (counted in ``stats["fp32_conv"]``).
 """
 import weakref
@@ -150,9 +152,15 @@ class QConv2d(nn.Conv2d):
                 self.qstep._version, self.qbits._version, ops.get_act_limbs(), self._content_gen)
 
     def hip_supported(self):
-        ok = (self.weight.is_cuda and self.dilation == (1, 1)
+        ok = (self.weight.is_cuda and self.dilation[0] == self.dilation[1]
               and self.padding_mode == "zeros" and self.stride[0] == self.stride[1]
               and self.padding[0] == self.padding[1])
+        if ok and self.dilation[0] != 1:
+            # the dilated 3x3 kernel (ops.conv2d_dilated_q): dense only, both weight forms packed() can produce
+            return self.groups == 1 and all(
+                ops.conv_dilated_supported(self.in_channels, self.out_channels, self.kernel_size[0],
+                                           self.kernel_size[1], self.stride[0], self.padding[0], self.dilation[0],
+                                           wlimbs=lw) for lw in (1, 3))
         if ok and self.groups != 1:
             # the grouped 3x3 kernel (ops.conv2d_grouped_q): both weight forms packed() can produce
             return all(ops.conv_grouped_supported(self.in_channels, self.out_channels, self.groups,
@@ -261,6 +269,8 @@ class QConv2d(nn.Conv2d):
             torch.zeros(self.out_channels, dtype=torch.float32, device=x.device)
         if self.groups != 1:
             y = ops.conv2d_grouped_q(xq, amax, codes, offset, self.stride[0], wscale.contiguous(), shift)
+        elif self.dilation[0] != 1:
+            y = ops.conv2d_dilated_q(xq, amax, codes, offset, self.dilation[0], wscale.contiguous(), shift)
         else:
             y = ops.tuned_conv2d_q(xq, amax, codes, offset, self.kernel_size[0], self.kernel_size[1],
                                    self.stride[0], self.padding[0], wscale.contiguous(), shift)
