@@ -801,6 +801,43 @@ int smpq_conv2d_dilated_fwd_q(const int8_t* xq, const float* x_absmax, int n, in
                               const float* col_shift, int relu, int limbs, float* y, float* y_absmax, int8_t* yq,
                               float yq_range, int32_t* overflow, smpq_stream_t stream);
 
+/* ---- narrow-channel dense conv (additions to ABI 7) ----------------------------------------------
+ * The conv2 and conv3 of a Bottleneck built with width_per_group != 64 (resnet.py:75-78): dense
+ * (groups 1, dilation 1) with cin % 16 == 0 but cin % 64 != 0 (csrc/conv_narrow.hip).
+ * smpq_conv2d_narrow_supported: 1 exactly for cin % 16 == 0, cin % 64 != 0, cout % 16 == 0, 3x3 /
+ *   pad 1 / stride 1 or 2 or 1x1 / pad 0 / stride 1, limbs == 3, wlimbs 1 or 3; else 0.
+ * Compact codes come from smpq_pack_weights_grouped with cg = cin: [wlimbs][cout][kh*kw*cin],
+ *   k = tap * cin + ci.
+ * smpq_weights_narrow_expand: compact codes -> the fragment-ordered copy the kernel reads, out
+ *   [planes][cout / 16][NK][64][16] int8 of smpq_weights_narrow_expand_bytes bytes (0 for an
+ *   unsupported operand), 16-B aligned. The kernel walks the input channels in slabs (all of them in
+ *   one slab when their halo patch fits LDS; the slab width depends on cin, the kernel size and the
+ *   stride, which is why both entries take them); within a slab of cwc 16-channel chunks k is ordered
+ *   [tap][chunk], byte b of lane i of step j is code (row 16 f + i % 16, chunk 4 j + i / 16, channel b
+ *   of the chunk), a slab ends in zero codes up to a whole step, and the slabs' steps follow one
+ *   another. wlimbs == 1 adds one plane that is 1 on the real K and 0 in the padding, from which the
+ *   kernel forms the window sums the weight offsets multiply. The copy is derived from the codes and
+ *   must be rebuilt whenever they change.
+ * smpq_conv2d_narrow_fwd_q: smpq_conv2d_fwd_q without a tile choice:
+ *   y = relu?(conv_real * col_scale[c] + col_shift[c] [+ residual]) as fp32 NHWC y and / or limb planes
+ *   yq at the static yq_range with the overflow flag; y_absmax optional; the residual as fp32 NHWC
+ *   `residual` or as limb planes residual_q with residual_range (not both). codes (compact) and
+ *   codes_expanded describe the same weights; the kernel reads the expanded copy. All three
+ *   activation planes together, and each output or residual tensor, stay below 2 GiB (SMPQ_E_SHAPE
+ *   otherwise: split the batch). SMPQ_E_SHAPE for a geometry smpq_conv2d_narrow_supported refuses,
+ *   SMPQ_E_INVALID for null or misaligned (16 B) pointers, two residuals or other limb counts, before
+ *   any launch. */
+int smpq_conv2d_narrow_supported(int cin, int cout, int kh, int kw, int stride, int pad, int limbs, int wlimbs);
+size_t smpq_weights_narrow_expand_bytes(int wlimbs, int cout, int cin, int kh, int kw, int stride);
+int smpq_weights_narrow_expand(const int8_t* codes, int wlimbs, int cout, int cin, int kh, int kw, int stride,
+                               int8_t* out, smpq_stream_t stream);
+int smpq_conv2d_narrow_fwd_q(const int8_t* xq, const float* x_absmax, int n, int h, int w, int cin,
+                             const int8_t* codes, const int8_t* codes_expanded, int wlimbs, const int32_t* offset,
+                             int cout, int kh, int kw, int stride, int pad, const float* col_scale,
+                             const float* col_shift, const float* residual, int relu, int limbs, float* y,
+                             float* y_absmax, int8_t* yq, float yq_range, int32_t* overflow,
+                             const int8_t* residual_q, float residual_range, smpq_stream_t stream);
+
 /* Diagnostics: one v_mfma_i32_16x16x64_i8 with the kernel's fragment mapping.
  *   a [16][64] int8 row-major, b [16][64] int8 (b[col][k]), c [16][16] int32 row-major */
 int smpq_debug_mfma_i8(const int8_t* a, const int8_t* b, int32_t* c, smpq_stream_t stream);

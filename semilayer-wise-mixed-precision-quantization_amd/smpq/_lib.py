@@ -128,6 +128,11 @@ _PROTOS = {
     "smpq_conv2d_dilated_supported": (_i, [_i] * 9),
     "smpq_conv2d_dilated_fwd_q": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp,
                                        _i, _i, _vp, _vp, _vp, ctypes.c_float, _vp, _vp]),
+    "smpq_conv2d_narrow_supported": (_i, [_i] * 8),
+    "smpq_weights_narrow_expand_bytes": (ctypes.c_size_t, [_i] * 6),
+    "smpq_weights_narrow_expand": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "smpq_conv2d_narrow_fwd_q": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp,
+                                      _i, _i, _vp, _vp, _vp, ctypes.c_float, _vp, _vp, ctypes.c_float, _vp]),
 }
 
 

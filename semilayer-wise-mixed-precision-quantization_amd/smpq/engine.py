@@ -240,6 +240,10 @@ def run_conv(conv, bn, act, relu, residual=None, want_amax=True, ctx=None, want_
                                         col_scale, col_shift)
         if special is not None and (residual is not None or res_q is not None):
             raise RuntimeError("smpq: residual on a grouped or dilated conv")
+        if special is None and conv.narrow():
+            # the narrow-channel kernel (conv2 / conv3 with width_per_group != 64): the residual in either form
+            special = functools.partial(ops.conv2d_narrow_q, act.limbs(), act.amax, codes, offset, col_scale, col_shift,
+                                        residual=residual, residual_q=res_q, residual_range=res_rng)
         if static:
             rng = ctx.ranges[id(conv)]
             if special is not None:

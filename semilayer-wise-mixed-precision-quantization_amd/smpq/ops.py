@@ -948,6 +948,125 @@ def conv2d_dilated_q(xq, x_absmax, codes, offset, dilation, col_scale, col_shift
     return out
 
 
+# ---- narrow-channel dense conv (include/smpq.h: conv2 / conv3 of a Bottleneck with width_per_group != 64) --
+# SMPQ_NARROW=0 puts every dense conv with cin % 64 != 0 back on torch (QConv2d.hip_supported then refuses it)
+NARROW = [os.environ.get("SMPQ_NARROW", "1") != "0"]
+
+
+def conv_narrow_supported(cin, cout, kh, kw, stride, pad, limbs=None, wlimbs=3):
+    """Does smpq_conv2d_narrow_fwd_q take this geometry (and is the SMPQ_NARROW switch on)?"""
+    limbs = get_act_limbs() if limbs is None else limbs
+    return NARROW[0] and bool(_lib.load().smpq_conv2d_narrow_supported(
+        int(cin), int(cout), int(kh), int(kw), int(stride), int(pad), int(limbs), int(wlimbs)))
+
+
+def pack_weights_narrow(w, step, wlimbs, stride):
+    """Weight codes of a dense conv with cin % 16 == 0, cin % 64 != 0 for conv2d_narrow_q: w fp32
+    [cout, cin, k, k] (k 3 or 1) -> (codes int8 [wlimbs, cout, k * k * cin], offset int32 [cout], wscale
+    fp32 [cout], status int32 [3] (device)), the rows coded as pack_weights_ex codes them. The
+    fragment-ordered copy the kernel reads (smpq_weights_narrow_expand; its channel slabs depend on the
+    conv's stride) is attached to ``codes`` and lives and dies with them."""
+    _req(w.is_cuda and w.dtype == torch.float32 and w.dim() == 4, "pack_weights_narrow: need a CUDA fp32 4-D weight")
+    _req(wlimbs in (1, 3), "pack_weights_narrow: wlimbs must be 1 or 3")
+    w = w.contiguous()
+    cout, cin, kh, kw = w.shape
+    stride = int(stride)
+    nbytes = int(_lib.load().smpq_weights_narrow_expand_bytes(int(wlimbs), cout, cin, kh, kw, stride))
+    _req(nbytes > 0, "pack_weights_narrow: not a conv the kernel takes (conv_narrow_supported)")
+    if step is not None:
+        step = step.to(device=w.device, dtype=torch.float32).contiguous()
+        _req(step.numel() == cout, "pack_weights_narrow: step length")
+    _req(wlimbs >= 2 or step is not None, "pack_weights_narrow: wlimbs=1 needs step")
+    codes = torch.empty(wlimbs, cout, kh * kw * cin, dtype=torch.int8, device=w.device)
+    offset = torch.zeros(cout, dtype=torch.int32, device=w.device)
+    wscale = torch.empty(cout, dtype=torch.float32, device=w.device)
+    status = torch.zeros(3, dtype=torch.int32, device=w.device)
+    _launch(w.device, "smpq_pack_weights_grouped", w, cout, cin, kh, kw, step, int(wlimbs), codes, offset, wscale, status)
+    expanded = torch.empty(nbytes, dtype=torch.int8, device=w.device)
+    _launch(w.device, "smpq_weights_narrow_expand", codes, int(wlimbs), cout, cin, kh, kw, stride, expanded)
+    codes._smpq_nx = expanded
+    codes._smpq_narrow = (kh, stride)
+    return codes, offset, wscale, status
+
+
+def conv2d_narrow_q(xq, x_absmax, codes, offset, col_scale, col_shift, residual=None, relu=False, y_absmax=None,
+                    out=None, emit_range=None, overflow=None, want_f32=True, residual_q=None, residual_range=None):
+    """Dense 3x3 / pad 1 / stride 1 or 2 or 1x1 / pad 0 / stride 1 conv on int8 limb planes xq
+    [3, n, h, w, cin], cin % 16 == 0 and cin % 64 != 0, with the codes of pack_weights_narrow (which
+    carry the kernel size and stride): y = conv(x, w) * s_x * col_scale + col_shift (+ res) (relu), NHWC
+    fp32; with ``emit_range`` also (or, with want_f32=False, only) the output's limb planes
+    [3, n, ho, wo, cout], returned as (y or None, yq), with ``overflow`` set when a value exceeded the
+    range. The residual is fp32 NHWC ``residual`` or limb planes ``residual_q`` with ``residual_range``,
+    as in conv2d_q. A batch whose tensors would reach 2 GiB runs in image chunks."""
+    _req(xq.is_cuda and xq.dtype == torch.int8 and xq.dim() == 5 and xq.is_contiguous(),
+         "narrow conv: xq must be [L,n,h,w,c] int8")
+    limbs, n, h, w, cin = xq.shape
+    expanded, geo = getattr(codes, "_smpq_nx", None), getattr(codes, "_smpq_narrow", None)
+    _req(expanded is not None and geo is not None and codes.dim() == 3, "narrow conv: codes of pack_weights_narrow")
+    k, stride = geo
+    pad = k // 2
+    wlimbs, cout, K = codes.shape
+    _req(K == k * k * cin and codes.dtype == torch.int8 and codes.is_contiguous() and codes.device == xq.device
+         and expanded.device == xq.device, "narrow conv: codes shape")
+    _req(conv_narrow_supported(cin, cout, k, k, stride, pad, limbs, wlimbs),
+         "narrow conv: unsupported geometry or limb counts (conv_narrow_supported)")
+    _req(offset is None or (offset.dtype == torch.int32 and offset.numel() == cout and wlimbs == 1),
+         "narrow conv: offset")
+    _req(x_absmax.dtype == torch.float32 and x_absmax.numel() == n, "narrow conv: x_absmax")
+    for t in (col_scale, col_shift):
+        _req(t.dtype == torch.float32 and t.numel() == cout and t.is_contiguous() and t.device == xq.device,
+             "narrow conv: col vectors")
+    ho, wo = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
+    yq = None
+    if emit_range is not None:
+        _req(emit_range > 0, "narrow conv: emit_range must be > 0")
+        _req(overflow is not None and overflow.dtype == torch.int32 and overflow.device == xq.device,
+             "narrow conv: overflow")
+        yq = torch.empty(limbs, n, ho, wo, cout, dtype=torch.int8, device=xq.device)
+    else:
+        want_f32 = True
+    if out is None and want_f32:
+        out = torch.empty(n, ho, wo, cout, dtype=torch.float32, device=xq.device)
+    _req(out is None or (out.shape == (n, ho, wo, cout) and out.is_contiguous()), "narrow conv: out shape")
+    if residual is not None:
+        _req(residual.shape == (n, ho, wo, cout) and residual.is_contiguous() and residual.dtype == torch.float32,
+             "narrow conv: residual shape")
+    if residual_q is not None:
+        _req(residual is None and residual_q.shape == (limbs, n, ho, wo, cout) and residual_q.dtype == torch.int8
+             and residual_q.is_contiguous() and residual_range is not None and residual_range > 0,
+             "narrow conv: residual_q")
+    if y_absmax is not None:
+        _req(y_absmax.numel() == n and y_absmax.dtype == torch.float32, "narrow conv: y_absmax")
+    # the kernel's 32-bit offsets run over all three limb planes of a tensor
+    per_img = max(limbs * h * w * cin, (limbs if (yq is not None or residual_q is not None) else 0) * ho * wo * cout,
+                  (4 if (out is not None or residual is not None) else 0) * ho * wo * cout)
+    chunks = _image_chunks(n, per_img, "narrow conv")
+    if chunks:
+        for i0, i1 in chunks:
+            r = conv2d_narrow_q(xq[:, i0:i1].contiguous(), x_absmax[i0:i1], codes, offset, col_scale, col_shift,
+                                residual=None if residual is None else residual[i0:i1], relu=relu,
+                                y_absmax=None if y_absmax is None else y_absmax[i0:i1],
+                                out=None if out is None else out[i0:i1], emit_range=emit_range, overflow=overflow,
+                                want_f32=want_f32,
+                                residual_q=None if residual_q is None else residual_q[:, i0:i1].contiguous(),
+                                residual_range=residual_range)
+            if yq is not None:
+                yq[:, i0:i1].copy_(r[1])
+        return (out, yq) if emit_range is not None else out
+    hook = _CONV_HOOK[0]
+    if hook is not None:
+        hook.begin()
+    _launch(xq.device, "smpq_conv2d_narrow_fwd_q", xq, x_absmax, n, h, w, cin, codes, expanded, int(wlimbs), offset,
+            cout, k, k, int(stride), pad, col_scale, col_shift, residual, 1 if relu else 0, int(limbs), out, y_absmax,
+            yq, float(emit_range or 0.0), overflow, residual_q, float(residual_range or 0.0))
+    if hook is not None:
+        hook.end(alg_work(n, h, w, cin, cout, k, k, ho, wo, limbs, wlimbs, out is not None, yq is not None,
+                          residual is not None, residual_q is not None))
+    if emit_range is not None:
+        return out, yq
+    return out
+
+
 def conv_pair_supported(cin, cout1, cout2, limbs=3):
     """Does smpq_conv2d_pair_fwd run this Bottleneck chain (conv3 cin -> cout1, next conv1 cout1 ->
     cout2)?"""

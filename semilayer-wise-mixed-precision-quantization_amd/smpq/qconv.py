@@ -18,9 +18,11 @@ with their fp32 weights in per-channel fixed point with as many int8 limbs as th
 (16 or 24 bits), counted in ``smpq.stats["fixed_conv"]``. The 7x7/2/3 stem on <= 4 channels runs
 as a 4x4 conv over space-to-depth pixels on the same kernel. A grouped 3x3 conv (ResNeXt) runs on
 the block-diagonal kernel of csrc/conv_grouped.hip, a dense 3x3 conv with padding = dilation 2, 4 or
-8 (replace_stride_with_dilation) on the phase-lattice kernel of csrc/conv_dilated.hip. Only geometries
-the kernels do not cover (other grouped convs, other dilations, grouped + dilated, other convs with
-cin % 64 != 0 or cout % 16 != 0) fall back to
+8 (replace_stride_with_dilation) on the phase-lattice kernel of csrc/conv_dilated.hip, a dense 3x3 / pad
+1 / stride 1 or 2 or 1x1 / stride 1 conv with cin % 16 == 0 but cin % 64 != 0 (width_per_group != 64) on
+the channel-slab kernel of csrc/conv_narrow.hip. Only geometries the kernels do not cover (other grouped
+convs, other dilations, grouped + dilated, grouped or dilated narrow convs, cin % 16 != 0, other kernel
+sizes or strides on cin % 64 != 0, cout % 16 != 0) fall back to
 ``F.conv2d`` on the GPU (counted in ``stats["fp32_conv"]``).
 """
 import weakref
@@ -166,7 +168,17 @@ class QConv2d(nn.Conv2d):
             return all(ops.conv_grouped_supported(self.in_channels, self.out_channels, self.groups,
                                                   self.kernel_size[0], self.kernel_size[1], self.stride[0],
                                                   self.padding[0], wlimbs=lw) for lw in (1, 3))
-        return ok and self.in_channels % 64 == 0 and self.out_channels % 16 == 0
+        if ok and self.in_channels % 64 != 0:
+            # the narrow-channel kernel (ops.conv2d_narrow_q): both weight forms packed() can produce
+            return self.kernel_size[0] == self.kernel_size[1] and all(
+                ops.conv_narrow_supported(self.in_channels, self.out_channels, self.kernel_size[0],
+                                          self.kernel_size[1], self.stride[0], self.padding[0], wlimbs=lw)
+                for lw in (1, 3))
+        return ok and self.out_channels % 16 == 0
+
+    def narrow(self):
+        """A dense conv on cin % 64 != 0 (the narrow-channel kernel's, when hip_supported())?"""
+        return self.groups == 1 and self.dilation[0] == 1 and self.in_channels % 64 != 0
 
     def packed(self):
         """Weight operand of the HIP conv: (codes int8 [LW, cout, K], LW, offset | None,
@@ -188,10 +200,14 @@ class QConv2d(nn.Conv2d):
             # compact per-group codes + the kernel's block-diagonal copy (ops.pack_weights_grouped)
             def pack(w, step, lw):
                 return ops.pack_weights_grouped(w, step, lw, self.groups)
+        elif self.narrow():
+            # compact codes + the kernel's fragment-ordered copy (ops.pack_weights_narrow)
+            def pack(w, step, lw):
+                return ops.pack_weights_narrow(w, step, lw, self.stride[0])
         else:
             pack = ops.pack_weights_ex
         with torch.no_grad():
-            if self.fully_quantized() and (self.in_channels % 64 == 0 or self.groups != 1):
+            if self.fully_quantized():
                 codes, offset, wscale, status = pack(w, self.qstep, 1)
                 st = status.cpu()
                 if int(st[0]) == 0 and int(st[1]) == 0:
@@ -271,6 +287,8 @@ class QConv2d(nn.Conv2d):
             y = ops.conv2d_grouped_q(xq, amax, codes, offset, self.stride[0], wscale.contiguous(), shift)
         elif self.dilation[0] != 1:
             y = ops.conv2d_dilated_q(xq, amax, codes, offset, self.dilation[0], wscale.contiguous(), shift)
+        elif self.narrow():
+            y = ops.conv2d_narrow_q(xq, amax, codes, offset, wscale.contiguous(), shift)
         else:
             y = ops.tuned_conv2d_q(xq, amax, codes, offset, self.kernel_size[0], self.kernel_size[1],
                                    self.stride[0], self.padding[0], wscale.contiguous(), shift)
