@@ -838,6 +838,32 @@ int smpq_conv2d_narrow_fwd_q(const int8_t* xq, const float* x_absmax, int n, int
                              float* y_absmax, int8_t* yq, float yq_range, int32_t* overflow,
                              const int8_t* residual_q, float residual_range, smpq_stream_t stream);
 
+/* ---- 3x3 small-channel stem (additions to ABI 7) -------------------------------------------------
+ * The conv1 of a CIFAR-style ResNet: dense 3x3 / stride 1 / pad 1 on cin <= 4 image channels
+ * (csrc/conv_stem3.hip). K = 9 taps x 4 channels = 36 bytes, one v_mfma_i32_16x16x64_i8 step.
+ * smpq_stem3_supported: 1 exactly for 3x3, stride 1, pad 1, 1 <= cin <= 4, cout % 64 == 0, limbs == 3,
+ *   wlimbs == 3; else 0.
+ * smpq_image_quantize_c4: x fp32 NCHW [n][c <= 4][h][w] -> out int8 [3][n][h][w][4] (4-B aligned), byte
+ *   ch of a pixel = channel ch quantized with the per-image absmax as smpq_act_quantize does with 3
+ *   limbs, zero for ch >= c.
+ * Weight operand: codes int8 [3][cout][64]: row c of limb l holds the 36 codes of
+ *   smpq_pack_weights_grouped (cg = 4, 3x3: k = tap * 4 + ci, the weight's channels zero-padded to 4)
+ *   followed by 28 zero bytes.
+ * smpq_stem_conv3_q: y = relu?(conv_real * col_scale[c] + col_shift[c]) as fp32 NHWC y and / or limb
+ *   planes yq [3][n][h][w][cout] at the static yq_range with the overflow flag; y_absmax optional. xq
+ *   are the planes of smpq_image_quantize_c4 whatever cin is. No residual and no weight offsets (a stem
+ *   operand always has 3 weight limbs). All three activation planes together, and each output tensor,
+ *   stay below 2 GiB (SMPQ_E_SHAPE otherwise: split the batch). SMPQ_E_SHAPE for a geometry
+ *   smpq_stem3_supported refuses, SMPQ_E_INVALID for null or misaligned (16 B) pointers, before any
+ *   launch. */
+int smpq_stem3_supported(int cin, int cout, int kh, int kw, int stride, int pad, int limbs, int wlimbs);
+int smpq_image_quantize_c4(const float* x, int n, int c, int h, int w, const float* absmax, int8_t* out,
+                           smpq_stream_t stream);
+int smpq_stem_conv3_q(const int8_t* xq, const float* x_absmax, int n, int h, int w, int cin, const int8_t* codes,
+                      int wlimbs, int cout, int kh, int kw, int stride, int pad, const float* col_scale,
+                      const float* col_shift, int relu, int limbs, float* y, float* y_absmax, int8_t* yq,
+                      float yq_range, int32_t* overflow, smpq_stream_t stream);
+
 /* Diagnostics: one v_mfma_i32_16x16x64_i8 with the kernel's fragment mapping.
  *   a [16][64] int8 row-major, b [16][64] int8 (b[col][k]), c [16][16] int32 row-major */
 int smpq_debug_mfma_i8(const int8_t* a, const int8_t* b, int32_t* c, smpq_stream_t stream);

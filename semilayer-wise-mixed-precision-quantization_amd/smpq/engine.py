@@ -8,6 +8,10 @@ and ``Bottleneck.forward`` (resnet.py:97-116):
   * stem conv 7x7/2 + BN + ReLU + MaxPool 3x3/2 (resnet.py:143-147): static mode, ONE launch
     (``stem_pool_s2d``: only the pooled limb planes leave the CU); dynamic mode, the stem conv
     (fp32 weights as 24-bit fixed point) then the pool fused with its output's quantization;
+  * the small-image (CIFAR-style) stem, conv1 3x3/1/1 on <= 4 channels with the max pool kept or
+    replaced by nn.Identity: ``image_quantize_c4`` (one dword per pixel and limb) + ``stem_conv3_q``
+    (csrc/conv_stem3.hip); static mode: limb planes only (then ``maxpool_limbs``), dynamic mode: fp32 +
+    max|y| (then ``maxpool_quantize`` or ``act_quantize``);
   * every block conv + its BN (+ residual add) (+ ReLU) = one ``conv2d_q`` launch; static mode:
     its epilogue writes the NEXT conv's limb planes, dynamic mode: fp32 + the per-image max|y| the
     next conv's quantizer needs;
@@ -479,16 +483,59 @@ def stem_s2d_plan(conv, bn):
     return _cached_plan(conv, bn, "_s2d_cache", build)
 
 
+def stem_c4_plan(conv, bn):
+    """The StemPlan of a 3x3 / stride 1 / pad 1 stem on <= 4 channels (ops.stem_conv3_q), or None when
+    conv1 is not one (QConv2d.c4_stem). Weights as in QConv2d.packed_c4."""
+    if not (isinstance(conv, QConv2d) and conv.c4_stem()):
+        return None
+
+    def build():
+        codes, wscale, kind = conv.packed_c4()
+        return StemPlan(codes, *_fold(conv, bn, wscale), kind)
+    return _cached_plan(conv, bn, "_c4_cache", build)
+
+
+def _stem_c4_forward(model, x, ctx, c4, pool):
+    """stem_forward for the small-image stem: conv1 3x3/1 + bn1 + relu on the one-step kernel, then the
+    3x3/2 max pool (``pool``) or nothing (nn.Identity)."""
+    codes, col_scale, col_shift, kind = c4
+    conv, n = model.conv1, x.shape[0]
+    amax_in = ops.act_absmax(x)
+    xq = ops.image_quantize_c4(x, amax_in)
+    stats["hip_conv"] += 1
+    if kind == "fixed":
+        stats["fixed_conv"] += 1
+    conv.last_path = "hip-%s-c4" % kind
+    if ctx is not None and ctx.ranges is not None and id(conv) in ctx.ranges:
+        # static range: the calibrated-range limb planes only (lean epilogue); the pool works on the codes
+        rng = ctx.ranges[id(conv)]
+        _, yq = ops.stem_conv3_q(xq, amax_in, codes, col_scale, col_shift, relu=True, emit_range=rng,
+                                 overflow=ctx.overflow, want_f32=False)
+        return Act(q=ops.maxpool_limbs(yq) if pool else yq, amax=ctx.range_tensor(conv), rng=rng)
+    yam = torch.zeros(n, dtype=torch.float32, device=x.device)
+    y = ops.stem_conv3_q(xq, amax_in, codes, col_scale, col_shift, relu=True, y_absmax=yam)
+    _record_max(ctx, conv, yam)
+    if pool:
+        q, f = ops.maxpool_quantize(y, yam, want_f32=True)
+        return Act(f32=f, q=q, amax=yam)
+    return Act(f32=y, q=ops.act_quantize(y, yam), amax=yam)
+
+
 def stem_forward(model, x, ctx=None):
     """conv1 7x7/2 + bn1 + relu + maxpool 3x3/2 (resnet.py:206-209) -> Act of the pooled output.
     Static-range mode: the stem writes its calibrated-range limb planes and the max pool works on
-    the codes (exact: the quantizer is monotone); no fp32 tensor is written. A stem the kernel does
-    not cover (not 7x7/2/3, or other input channels than the conv's) runs on torch, counted in
-    stats['fp32_conv'] like every such conv."""
+    the codes (exact: the quantizer is monotone); no fp32 tensor is written. The small-image variant
+    (conv1 3x3/1/1 on <= 4 channels, maxpool kept or replaced by nn.Identity) runs the same way on
+    ops.stem_conv3_q. A stem the kernels do not cover (another geometry, or other input channels than the
+    conv's) runs on torch, counted in stats['fp32_conv'] like every such conv."""
     x = x.float().contiguous()
     n = x.shape[0]
     pool_ok = isinstance(model.maxpool, torch.nn.MaxPool2d) and model.maxpool.kernel_size in (3, (3, 3)) \
         and model.maxpool.stride in (2, (2, 2)) and model.maxpool.padding in (1, (1, 1))
+    if (pool_ok or isinstance(model.maxpool, torch.nn.Identity)) and x.shape[1] == model.conv1.in_channels:
+        c4 = stem_c4_plan(model.conv1, model.bn1)
+        if c4 is not None:
+            return _stem_c4_forward(model, x, ctx, c4, pool_ok)
     s2d = stem_s2d_plan(model.conv1, model.bn1) if (pool_ok and x.shape[1] == model.conv1.in_channels
                                                     and x.shape[2] >= 2 and x.shape[3] >= 2) else None
     if s2d is not None:

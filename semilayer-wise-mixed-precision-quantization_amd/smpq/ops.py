@@ -1067,6 +1067,112 @@ def conv2d_narrow_q(xq, x_absmax, codes, offset, col_scale, col_shift, residual=
     return out
 
 
+# ---- 3x3 small-channel stem (include/smpq.h: the conv1 of a CIFAR-style ResNet) ----------------------
+# SMPQ_STEM3=0 puts the 3x3 / stride 1 stem on <= 4 channels back on torch (QConv2d.c4_stem then refuses it)
+STEM3 = [os.environ.get("SMPQ_STEM3", "1") != "0"]
+
+
+def stem3_supported(cin, cout, kh, kw, stride, pad, limbs=None, wlimbs=3):
+    """Does smpq_stem_conv3_q take this geometry (and is the SMPQ_STEM3 switch on)?"""
+    limbs = get_act_limbs() if limbs is None else limbs
+    return STEM3[0] and bool(_lib.load().smpq_stem3_supported(
+        int(cin), int(cout), int(kh), int(kw), int(stride), int(pad), int(limbs), int(wlimbs)))
+
+
+def image_quantize_c4(x, x_absmax):
+    """NCHW fp32 images (c <= 4) -> 3 limb planes [3, n, h, w, 4], one dword per pixel and limb, the
+    channels c..3 zero: the input of stem_conv3_q, quantized as act_quantize quantizes."""
+    _req(x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous() and 1 <= x.shape[1] <= 4,
+         "image_quantize_c4: need contiguous NCHW fp32 with <= 4 channels")
+    n, c, h, w = x.shape
+    _req(n > 0 and h > 0 and w > 0, "image_quantize_c4: empty image")
+    _req(x_absmax.numel() == n and x_absmax.dtype == torch.float32 and x_absmax.device == x.device,
+         "image_quantize_c4: absmax")
+    out = torch.empty(3, n, h, w, 4, dtype=torch.int8, device=x.device)
+    _launch(x.device, "smpq_image_quantize_c4", x, n, c, h, w, x_absmax, out)
+    return out
+
+
+def pack_weights_stem3(w, step=None):
+    """3x3 stem weight fp32 [cout, c <= 4, 3, 3] -> (codes int8 [3, cout, 64], wscale fp32 [cout], status
+    int32 [3] (device)): the rows of pack_weights_ex's coder on the weight zero-padded to 4 channels, K
+    ordered [tap][channel] (36 bytes), then zero-padded to the 64 bytes of one MFMA step. Channels with
+    a recorded quantization step (``step`` [cout], 0 = never quantized) are exact codes, the others
+    24-bit per-channel fixed point; status[2] counts the latter."""
+    _req(w.is_cuda and w.dtype == torch.float32 and w.dim() == 4 and tuple(w.shape[2:]) == (3, 3)
+         and 1 <= w.shape[1] <= 4, "pack_weights_stem3: need a CUDA fp32 [cout, <=4, 3, 3] weight")
+    cout, cin = w.shape[:2]
+    w4 = torch.zeros(cout, 4, 3, 3, dtype=torch.float32, device=w.device)
+    w4[:, :cin] = w
+    if step is not None:
+        step = step.to(device=w.device, dtype=torch.float32).contiguous()
+        _req(step.numel() == cout, "pack_weights_stem3: step length")
+    codes = torch.empty(3, cout, 36, dtype=torch.int8, device=w.device)
+    offset = torch.zeros(cout, dtype=torch.int32, device=w.device)
+    wscale = torch.empty(cout, dtype=torch.float32, device=w.device)
+    status = torch.zeros(3, dtype=torch.int32, device=w.device)
+    _launch(w.device, "smpq_pack_weights_grouped", w4, cout, 4, 3, 3, step, 3, codes, offset, wscale, status)
+    return torch.nn.functional.pad(codes, (0, 28)).contiguous(), wscale, status
+
+
+def stem_conv3_q(xq, x_absmax, codes, col_scale, col_shift, relu=True, y_absmax=None, out=None, emit_range=None,
+                 overflow=None, want_f32=True):
+    """The 3x3 / stride 1 / pad 1 stem conv on the planes of image_quantize_c4 ([3, n, h, w, 4]) with the
+    codes of pack_weights_stem3 ([3, cout, 64], cout % 64 == 0): y = conv(x, w) * s_x * col_scale +
+    col_shift (relu), NHWC fp32 [n, h, w, cout]; with ``emit_range`` also (or, with want_f32=False, only)
+    the output's limb planes [3, n, h, w, cout], returned as (y or None, yq), with ``overflow`` set when a
+    value exceeded the range. A batch whose tensors would reach 2 GiB runs in image chunks."""
+    _req(xq.is_cuda and xq.dtype == torch.int8 and xq.dim() == 5 and xq.is_contiguous() and xq.shape[0] == 3
+         and xq.shape[4] == 4, "stem conv3: xq must be [3,n,h,w,4] int8 (image_quantize_c4)")
+    limbs, n, h, w, _ = xq.shape
+    _req(codes.dim() == 3 and codes.shape[2] == 64 and codes.dtype == torch.int8 and codes.is_contiguous()
+         and codes.device == xq.device, "stem conv3: codes of pack_weights_stem3")
+    wlimbs, cout, _ = codes.shape
+    _req(stem3_supported(4, cout, 3, 3, 1, 1, limbs, wlimbs),
+         "stem conv3: unsupported geometry or limb counts (stem3_supported)")
+    _req(x_absmax.dtype == torch.float32 and x_absmax.numel() == n, "stem conv3: x_absmax")
+    for t in (col_scale, col_shift):
+        _req(t.dtype == torch.float32 and t.numel() == cout and t.is_contiguous() and t.device == xq.device,
+             "stem conv3: col vectors")
+    yq = None
+    if emit_range is not None:
+        _req(emit_range > 0, "stem conv3: emit_range must be > 0")
+        _req(overflow is not None and overflow.dtype == torch.int32 and overflow.device == xq.device,
+             "stem conv3: overflow")
+        yq = torch.empty(limbs, n, h, w, cout, dtype=torch.int8, device=xq.device)
+    else:
+        want_f32 = True
+    if out is None and want_f32:
+        out = torch.empty(n, h, w, cout, dtype=torch.float32, device=xq.device)
+    _req(out is None or (out.shape == (n, h, w, cout) and out.is_contiguous() and out.dtype == torch.float32),
+         "stem conv3: out shape")
+    if y_absmax is not None:
+        _req(y_absmax.numel() == n and y_absmax.dtype == torch.float32, "stem conv3: y_absmax")
+    # the kernel's 32-bit offsets run over all three limb planes of a tensor
+    per_img = max(limbs * h * w * 4, (limbs if yq is not None else 0) * h * w * cout,
+                  (4 if out is not None else 0) * h * w * cout)
+    chunks = _image_chunks(n, per_img, "stem conv3")
+    if chunks:
+        for i0, i1 in chunks:
+            r = stem_conv3_q(xq[:, i0:i1].contiguous(), x_absmax[i0:i1], codes, col_scale, col_shift, relu=relu,
+                             y_absmax=None if y_absmax is None else y_absmax[i0:i1],
+                             out=None if out is None else out[i0:i1], emit_range=emit_range, overflow=overflow,
+                             want_f32=want_f32)
+            if yq is not None:
+                yq[:, i0:i1].copy_(r[1])
+        return (out, yq) if emit_range is not None else out
+    hook = _CONV_HOOK[0]
+    if hook is not None:
+        hook.begin()
+    _launch(xq.device, "smpq_stem_conv3_q", xq, x_absmax, n, h, w, 4, codes, int(wlimbs), cout, 3, 3, 1, 1, col_scale,
+            col_shift, 1 if relu else 0, int(limbs), out, y_absmax, yq, float(emit_range or 0.0), overflow)
+    if hook is not None:
+        hook.end(alg_work(n, h, w, 4, cout, 3, 3, h, w, limbs, wlimbs, out is not None, yq is not None, False, False))
+    if emit_range is not None:
+        return out, yq
+    return out
+
+
 def conv_pair_supported(cin, cout1, cout2, limbs=3):
     """Does smpq_conv2d_pair_fwd run this Bottleneck chain (conv3 cin -> cout1, next conv1 cout1 ->
     cout2)?"""

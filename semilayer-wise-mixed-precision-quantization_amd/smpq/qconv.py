@@ -20,7 +20,9 @@ as a 4x4 conv over space-to-depth pixels on the same kernel. A grouped 3x3 conv 
 the block-diagonal kernel of csrc/conv_grouped.hip, a dense 3x3 conv with padding = dilation 2, 4 or
 8 (replace_stride_with_dilation) on the phase-lattice kernel of csrc/conv_dilated.hip, a dense 3x3 / pad
 1 / stride 1 or 2 or 1x1 / stride 1 conv with cin % 16 == 0 but cin % 64 != 0 (width_per_group != 64) on
-the channel-slab kernel of csrc/conv_narrow.hip. Only geometries the kernels do not cover (other grouped
+the channel-slab kernel of csrc/conv_narrow.hip, the 3x3 / stride 1 / pad 1 stem on <= 4 channels of a
+small-image (CIFAR-style) ResNet, with cout % 64 == 0 and 3 activation limbs, on the one-step kernel of
+csrc/conv_stem3.hip (``c4_stem`` / ``packed_c4``, like the 7x7 stem outside ``packed()``). Only geometries the kernels do not cover (other grouped
 convs, other dilations, grouped + dilated, grouped or dilated narrow convs, cin % 16 != 0, other kernel
 sizes or strides on cin % 64 != 0, cout % 16 != 0) fall back to
 ``F.conv2d`` on the GPU (counted in ``stats["fp32_conv"]``).
@@ -247,10 +249,49 @@ class QConv2d(nn.Conv2d):
         self._s2d_pack = (key, res)
         return res
 
+    def c4_stem(self):
+        """Is this the 3x3 / stride 1 / pad 1 stem on <= 4 channels (the conv1 of a CIFAR-style ResNet)
+        that runs on the one-step kernel of csrc/conv_stem3.hip (3 activation limbs, ops.STEM3 on)?"""
+        return (self.weight.is_cuda and self.groups == 1 and self.dilation == (1, 1) and self.padding_mode == "zeros"
+                and self.stride[0] == self.stride[1] and self.padding[0] == self.padding[1]
+                and ops.stem3_supported(self.in_channels, self.out_channels, self.kernel_size[0], self.kernel_size[1],
+                                        self.stride[0], self.padding[0]))
+
+    def packed_c4(self):
+        """Weight operand of the 3x3 small-channel stem: (codes int8 [3, cout, 64], wscale fp32 [cout],
+        kind); quantized channels as exact codes, the others in 24-bit per-channel fixed point (kind
+        'fixed' when any channel is, else 'exact16'), as in packed_s2d."""
+        key = self._pack_key()
+        cached = getattr(self, "_c4_pack", None)
+        if cached is not None and cached[0] == key:
+            return cached[1]
+        with torch.no_grad():
+            quantized = (self._bits_host > 0).any()
+            codes, wscale, status = ops.pack_weights_stem3(self.weight.detach().float(),
+                                                           step=self.qstep if quantized else None)
+        res = (codes, wscale, "fixed" if int(status.cpu()[2]) > 0 else "exact16")
+        stats["repack"] += 1
+        self._c4_pack = (key, res)
+        return res
+
     # ---- forward (module path; the fused ResNet path is smpq.engine) ------------------------
     def forward(self, x):
         if not x.is_cuda:
             raise RuntimeError("smpq QConv2d is MI355X-native: move the model and input to the GPU")
+        if x.shape[1] == self.in_channels and self.c4_stem():
+            # the 3x3 / stride 1 stem of a small-image ResNet: one dword per pixel and limb on the one-step
+            # kernel, the same codes and results as the engine's stem (engine.stem_c4_plan)
+            codes, c4_scale, kind = self.packed_c4()
+            stats["hip_conv"] += 1
+            if kind == "fixed":
+                stats["fixed_conv"] += 1
+            self.last_path = "hip-%s-c4" % kind
+            xc = x.float().contiguous()
+            amax = ops.act_absmax(xc)
+            shift = self.bias.detach().float().contiguous() if self.bias is not None else \
+                torch.zeros(self.out_channels, dtype=torch.float32, device=x.device)
+            y = ops.stem_conv3_q(ops.image_quantize_c4(xc, amax), amax, codes, c4_scale.contiguous(), shift, relu=False)
+            return y.permute(0, 3, 1, 2)
         if self.s2d_stem() and x.shape[1] == self.in_channels and x.shape[2] >= 2 and x.shape[3] >= 2:
             # the reference's 7x7/2/3 stem (resnet.py:143): space-to-depth planes on the conv kernel,
             # the same codes and results as the engine's stem (engine.stem_s2d_plan)
