@@ -6,48 +6,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from family_cases import DILATED_SHAPES as SHAPES, dilated_case
 from lean_ref import check_codes, emit_range_for, expected_overflow, to_code_units
-from test_gpu import LIMB_QMAX, emulate_limbs
+from test_gpu import LIMB_QMAX
 
 pytestmark = pytest.mark.gpu
-
-# (cin, cout, d, H, W): odd size (lattices of 5 and 4); two input chunks, a partial second row tile, non-square;
-# two channel tiles, lattices of 2 and 1; a second row tile for phase row 0 only; d > H (empty phases, row
-# taps all outside)
-SHAPES = [(64, 64, 2, 9, 9), (128, 64, 2, 18, 12), (64, 128, 4, 7, 7), (128, 64, 4, 33, 10), (64, 64, 8, 5, 11)]
-_CASES = {}
-
-
-def dilated_case(gpu, shape, wl):
-    """Operands on the GPU and the reference (y, bound before ReLU) on the host, built once per (shape, wl)."""
-    if (shape, wl) in _CASES:
-        return _CASES[(shape, wl)]
-    from smpq import ops
-    cin, cout, d, h, w_ = shape
-    g = torch.Generator().manual_seed(cin + cout + d + h + 10 * wl)
-    w = (torch.randn(cout, cin, 3, 3, generator=g) * 0.1).to(gpu)
-    step = ops.quantize_channels_(w.reshape(cout, -1), [8] * cout) if wl == 1 else None
-    codes, offset, wscale, st = ops.pack_weights_ex(w, step, wl)
-    assert st.cpu().tolist() == ([0, 0, 0] if wl == 1 else [0, 0, cout])
-    assert wl == 3 or bool((offset != 0).any())
-    x = torch.randn(2, h, w_, cin, generator=g)
-    x[1] *= 7.0  # different per-image ranges
-    xd = x.to(gpu)
-    am = ops.act_absmax(xd)
-    xq = ops.act_quantize(xd, am, 3)
-    cs = (wscale * torch.linspace(0.5, 1.5, cout, device=gpu)).contiguous()
-    sh = torch.linspace(-0.1, 0.1, cout, device=gpu).contiguous()
-    # the zero-inflated weight: code (+ offset) at pitch d of a (2d+1) x (2d+1) kernel, 0 elsewhere
-    m = codes.cpu().numpy().astype(np.int64).reshape(wl, cout, 3, 3, cin)
-    if wl == 1:
-        m = m + offset.cpu().numpy().astype(np.int64).reshape(1, cout, 1, 1, 1)
-    big = np.zeros((wl, cout, 2 * d + 1, 2 * d + 1, cin), dtype=np.int64)
-    big[:, :, ::d, ::d, :] = m
-    rscale = (am.cpu().numpy() * np.float32(1.0 / LIMB_QMAX[3])).astype(np.float64)
-    y, bound = emulate_limbs(xq.cpu().numpy(), big, 2 * d + 1, 1, d, rscale, cs.cpu().numpy().astype(np.float64),
-                             sh.cpu().numpy().astype(np.float64), None, False)
-    _CASES[(shape, wl)] = (xq, am, codes, offset if wl == 1 else None, cs, sh, y, bound)
-    return _CASES[(shape, wl)]
 
 
 @pytest.mark.parametrize("relu", [0, 1])
@@ -55,7 +18,9 @@ def dilated_case(gpu, shape, wl):
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "c%d_o%d_d%d_h%d_w%d" % s)
 def test_dilated_kernel_vs_emulation(gpu, shape, wl, relu):
     from smpq import ops
-    xq, am, codes, offset, cs, sh, y, bound = dilated_case(gpu, shape, wl)
+    case = dilated_case(gpu, shape, wl)
+    xq, am, codes, offset, cs, sh = case.operands
+    y, bound = case.reference()
     d = shape[2]
     ye = np.maximum(y, 0) if relu else y
     yam = torch.zeros(2, device=gpu)

@@ -6,50 +6,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from family_cases import GROUPED_SHAPES as SHAPES, grouped_case
 from lean_ref import check_codes, emit_range_for, expected_overflow, to_code_units
-from test_gpu import LIMB_QMAX, emulate_limbs
+from test_gpu import LIMB_QMAX
 
 pytestmark = pytest.mark.gpu
-
-# (cin, cout, groups, stride, H): 4 groups / fragment, odd size; stride 2, even; one group / fragment;
-# a fragment is half a group, stride 2, odd; cg 64, og 128; cg != og
-SHAPES = [(64, 64, 16, 1, 9), (128, 128, 16, 2, 10), (64, 64, 4, 1, 7), (128, 128, 4, 2, 9), (128, 256, 2, 1, 5),
-          (64, 128, 4, 1, 6), (48, 48, 3, 1, 5)]  # the last: three fragments, the workgroup's fourth wave idle
-_CASES = {}
-
-
-def grouped_case(gpu, shape, wl):
-    """Operands on the GPU and the reference (y, bound before ReLU) on the host, built once per (shape, wl)."""
-    if (shape, wl) in _CASES:
-        return _CASES[(shape, wl)]
-    from smpq import ops
-    cin, cout, groups, stride, h = shape
-    cg, og = cin // groups, cout // groups
-    g = torch.Generator().manual_seed(cin + cout + groups + 10 * wl)
-    w = (torch.randn(cout, cg, 3, 3, generator=g) * 0.1).to(gpu)
-    step = ops.quantize_channels_(w.reshape(cout, -1), [8] * cout) if wl == 1 else None
-    codes, offset, wscale, st = ops.pack_weights_grouped(w, step, wl, groups)
-    assert st.cpu().tolist() == ([0, 0, 0] if wl == 1 else [0, 0, cout])
-    assert wl == 3 or bool((offset != 0).any())
-    x = torch.randn(2, h, h, cin, generator=g)
-    x[1] *= 7.0  # different per-image ranges
-    xd = x.to(gpu)
-    am = ops.act_absmax(xd)
-    xq = ops.act_quantize(xd, am, 3)
-    cs = (wscale * torch.linspace(0.5, 1.5, cout, device=gpu)).contiguous()
-    sh = torch.linspace(-0.1, 0.1, cout, device=gpu).contiguous()
-    # dense block-diagonal weight: code (+ offset) inside the row's group, 0 outside
-    m = codes.cpu().numpy().astype(np.int64).reshape(wl, cout, 3, 3, cg)
-    if wl == 1:
-        m = m + offset.cpu().numpy().astype(np.int64).reshape(1, cout, 1, 1, 1)
-    dense = np.zeros((wl, cout, 3, 3, cin), dtype=np.int64)
-    for c in range(cout):
-        dense[:, c, :, :, (c // og) * cg:(c // og + 1) * cg] = m[:, c]
-    rscale = (am.cpu().numpy() * np.float32(1.0 / LIMB_QMAX[3])).astype(np.float64)
-    y, bound = emulate_limbs(xq.cpu().numpy(), dense, 3, stride, 1, rscale, cs.cpu().numpy().astype(np.float64),
-                             sh.cpu().numpy().astype(np.float64), None, False)
-    _CASES[(shape, wl)] = (xq, am, codes, offset if wl == 1 else None, cs, sh, y, bound)
-    return _CASES[(shape, wl)]
 
 
 @pytest.mark.parametrize("relu", [0, 1])
@@ -57,7 +18,9 @@ def grouped_case(gpu, shape, wl):
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "c%d_o%d_g%d_s%d_h%d" % s)
 def test_grouped_kernel_vs_emulation(gpu, shape, wl, relu):
     from smpq import ops
-    xq, am, codes, offset, cs, sh, y, bound = grouped_case(gpu, shape, wl)
+    case = grouped_case(gpu, shape, wl)
+    xq, am, codes, offset, cs, sh = case.operands
+    y, bound = case.reference()
     stride = shape[3]
     ye = np.maximum(y, 0) if relu else y
     yam = torch.zeros(2, device=gpu)

@@ -6,49 +6,13 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from family_cases import NARROW_SHAPES as SHAPES, narrow_case
 from lean_ref import check_codes, decode, emit_range_for, expected_overflow, residual_planes, to_code_units
-from test_gpu import LIMB_QMAX, emulate_limbs
+from test_gpu import LIMB_QMAX
 
 pytestmark = pytest.mark.gpu
 
-# (cin, cout, k, stride, H, W): smallest K, padded last step, one active wave; stride 2, odd and non-square;
-# partial last workgroup, partial column tile; 1x1 with K = 1.5 steps; streamed weights (23 steps); at stride 2
-# the widest cin staged in one slab (11 chunks) and the narrowest that takes two (13 = 11 + 2)
-SHAPES = [(16, 16, 3, 1, 9, 9), (32, 64, 3, 2, 9, 11), (48, 80, 3, 1, 7, 18), (96, 32, 1, 1, 5, 13),
-          (160, 64, 3, 1, 10, 8), (176, 16, 3, 2, 9, 9), (208, 16, 3, 2, 9, 9)]
 ONE_BY_ONE = [s for s in SHAPES if s[2] == 1]
-_CASES = {}
-
-
-def narrow_case(gpu, shape, wl):
-    """Operands on the GPU and what the reference needs on the host, built once per (shape, wl)."""
-    if (shape, wl) in _CASES:
-        return _CASES[(shape, wl)]
-    from smpq import ops
-    cin, cout, k, stride, h, w_ = shape
-    g = torch.Generator().manual_seed(cin + cout + k + h + 10 * wl)
-    w = (torch.randn(cout, cin, k, k, generator=g) * 0.1).to(gpu)
-    step = ops.quantize_channels_(w.reshape(cout, -1), [8] * cout) if wl == 1 else None
-    codes, offset, wscale, st = ops.pack_weights_narrow(w, step, wl, stride)
-    assert st.cpu().tolist() == ([0, 0, 0] if wl == 1 else [0, 0, cout])
-    assert wl == 3 or bool((offset != 0).any())
-    x = torch.randn(2, h, w_, cin, generator=g)
-    x[1] *= 7.0  # different per-image ranges
-    xd = x.to(gpu)
-    am = ops.act_absmax(xd)
-    xq = ops.act_quantize(xd, am, 3)
-    cs = (wscale * torch.linspace(0.5, 1.5, cout, device=gpu)).contiguous()
-    sh = torch.linspace(-0.1, 0.1, cout, device=gpu).contiguous()
-    m = codes.cpu().numpy().astype(np.int64).reshape(wl, cout, k, k, cin)
-    if wl == 1:
-        m = m + offset.cpu().numpy().astype(np.int64).reshape(1, cout, 1, 1, 1)
-    rscale = (am.cpu().numpy() * np.float32(1.0 / LIMB_QMAX[3])).astype(np.float64)
-
-    def ref(residual=None):  # (y, bound) before ReLU
-        return emulate_limbs(xq.cpu().numpy(), m, k, stride, k // 2, rscale, cs.cpu().numpy().astype(np.float64),
-                             sh.cpu().numpy().astype(np.float64), residual, False)
-    _CASES[(shape, wl)] = (xq, am, codes, offset if wl == 1 else None, cs, sh, ref)
-    return _CASES[(shape, wl)]
 
 
 def check_forms(gpu, ops_args, y, bound, relu, **res):
@@ -78,9 +42,9 @@ def check_forms(gpu, ops_args, y, bound, relu, **res):
 @pytest.mark.parametrize("wl", [1, 3])
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "c%d_o%d_k%d_s%d_h%d_w%d" % s)
 def test_narrow_kernel_vs_emulation(gpu, shape, wl, relu):
-    xq, am, codes, offset, cs, sh, ref = narrow_case(gpu, shape, wl)
-    y, bound = ref()
-    check_forms(gpu, (xq, am, codes, offset, cs, sh), y, bound, relu)
+    case = narrow_case(gpu, shape, wl)
+    y, bound = case.reference()
+    check_forms(gpu, case.operands, y, bound, relu)
 
 
 @pytest.mark.parametrize("form", ["fp32", "planes"])
@@ -88,7 +52,7 @@ def test_narrow_kernel_vs_emulation(gpu, shape, wl, relu):
 @pytest.mark.parametrize("wl", [1, 3])
 @pytest.mark.parametrize("shape", ONE_BY_ONE, ids=lambda s: "c%d_o%d_k%d_s%d_h%d_w%d" % s)
 def test_narrow_1x1_residual(gpu, shape, wl, relu, form):
-    xq, am, codes, offset, cs, sh, ref = narrow_case(gpu, shape, wl)
+    case = narrow_case(gpu, shape, wl)
     _, cout, _, _, h, w_ = shape
     if form == "fp32":
         r = torch.randn(2, h, w_, cout, generator=torch.Generator().manual_seed(9)).to(gpu)
@@ -97,8 +61,8 @@ def test_narrow_1x1_residual(gpu, shape, wl, relu, form):
         rq, rr = residual_planes(gpu, 2, h, w_, cout, 3, 9)
         res = {"residual_q": rq, "residual_range": rr}
         rhost = decode(rq).astype(np.float64) * np.float64(np.float32(rr) / np.float32(LIMB_QMAX[3]))
-    y, bound = ref(rhost)
-    check_forms(gpu, (xq, am, codes, offset, cs, sh), y, bound, relu, **res)
+    y, bound = case.reference(residual=rhost)
+    check_forms(gpu, case.operands, y, bound, relu, **res)
 
 
 @pytest.mark.parametrize("free_channel,path", [(False, "hip-exact8"), (True, "hip-fixed")])

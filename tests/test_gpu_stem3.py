@@ -6,49 +6,20 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from family_cases import STEM3_SHAPES as SHAPES, stem3_case
 from lean_ref import check_codes, emit_range_for, expected_overflow, to_code_units
-from test_gpu import LIMB_QMAX, emulate_limbs
+from test_gpu import LIMB_QMAX
 
 pytestmark = pytest.mark.gpu
-
-# (c, cout, H, W) on 8-row x 16-column tiles: whole rows of a tile; partial tiles on both axes, two tiles per
-# axis; one channel, two channel tiles, an image smaller than a tile; all four channels, a last row tile of one
-# row; 2 * 17 * 16 = 544 tiles for the 512 workgroups of the launch (the smallest walk of two tiles, the last
-# tiles partial on both axes: it replaces (3, 64, 33, 34), which gives every tile its own workgroup)
-SHAPES = [(3, 64, 8, 8), (3, 64, 9, 19), (1, 128, 5, 3), (4, 64, 17, 16), (3, 64, 129, 250)]
-_CASES = {}
-
-
-def stem3_case(gpu, shape):
-    """Operands on the GPU and the reference (y, bound before ReLU) on the host, built once per shape."""
-    if shape in _CASES:
-        return _CASES[shape]
-    from smpq import ops
-    c, cout, h, w_ = shape
-    g = torch.Generator().manual_seed(c + cout + h + w_)
-    w = (torch.randn(cout, c, 3, 3, generator=g) * 0.1).to(gpu)
-    codes, wscale, st = ops.pack_weights_stem3(w)
-    assert st.cpu().tolist() == [0, 0, cout] and not bool(codes[:, :, 36:].any())
-    x = torch.randn(2, c, h, w_, generator=g)
-    x[1] *= 7.0  # different per-image ranges
-    xd = x.to(gpu)
-    am = ops.act_absmax(xd)
-    xq = ops.image_quantize_c4(xd, am)
-    cs = (wscale * torch.linspace(0.5, 1.5, cout, device=gpu)).contiguous()
-    sh = torch.linspace(-0.1, 0.1, cout, device=gpu).contiguous()
-    m = codes[:, :, :36].cpu().numpy().astype(np.int64).reshape(3, cout, 3, 3, 4)
-    rscale = (am.cpu().numpy() * np.float32(1.0 / LIMB_QMAX[3])).astype(np.float64)
-    y, bound = emulate_limbs(xq.cpu().numpy(), m, 3, 1, 1, rscale, cs.cpu().numpy().astype(np.float64),
-                             sh.cpu().numpy().astype(np.float64), None, False)
-    _CASES[shape] = (xq, am, codes, cs, sh, y, bound)
-    return _CASES[shape]
 
 
 @pytest.mark.parametrize("relu", [0, 1])
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "c%d_o%d_h%d_w%d" % s)
 def test_stem3_kernel_vs_emulation(gpu, shape, relu):
     from smpq import ops
-    xq, am, codes, cs, sh, y, bound = stem3_case(gpu, shape)
+    case = stem3_case(gpu, shape)
+    xq, am, codes, _, cs, sh = case.operands
+    y, bound = case.reference()
     ye = np.maximum(y, 0) if relu else y
     yam = torch.zeros(2, device=gpu)
     yk = ops.stem_conv3_q(xq, am, codes, cs, sh, relu=bool(relu), y_absmax=yam).cpu().numpy()
