@@ -125,7 +125,8 @@ int smpq_pack_weights_ex(const float* w, int cout, int cin, int kh, int kw, cons
                          int wlimbs, int8_t* codes, int32_t* offset, float* wscale, int32_t* status,
                          smpq_stream_t stream);
 
-/* Per-image absolute maximum, accumulated with atomicMax into absmax[n] (caller zeroes). */
+/* Per-image absolute maximum, accumulated with atomicMax into absmax[n] (caller zeroes).
+ * n <= 65535 (SMPQ_E_SHAPE otherwise, before any launch). */
 int smpq_act_absmax(const float* x, int n, int64_t per_image, float* absmax,
                     smpq_stream_t stream);
 

@@ -51,7 +51,7 @@ __global__ __launch_bounds__(256) void act_quantize_kernel(const float* __restri
     const long long e = v * 8;
     const int img = (int)(e / per_image);
     const float am = absmax[img];
-    const float inv = am > 0.f ? qmax / am : 0.f;
+    const ActScale scale = act_scale<L>(am);
     const float4 x0 = *reinterpret_cast<const float4*>(x + e);
     const float4 x1 = *reinterpret_cast<const float4*>(x + e + 4);
     const float vals[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
@@ -60,7 +60,7 @@ __global__ __launch_bounds__(256) void act_quantize_kernel(const float* __restri
     for (int l = 0; l < L; ++l) lo[l] = hi[l] = 0u;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      float qf = rintf(vals[k] * inv);
+      float qf = rintf(scale(vals[k]));
       qf = fminf(fmaxf(qf, -qmax), qmax);
       int d[L];
       split_limbs<L>((int)qf, d);
@@ -97,7 +97,7 @@ __global__ __launch_bounds__(256) void image_quantize_s2d_kernel(const float* __
     const int i = (int)(t % h2);
     const int img = (int)(t / h2);
     const float am = absmax[img];
-    const float inv = am > 0.f ? qmax / am : 0.f;
+    const ActScale scale = act_scale<L>(am);
     unsigned int word[L][4];
 #pragma unroll
     for (int l = 0; l < L; ++l)
@@ -119,7 +119,7 @@ __global__ __launch_bounds__(256) void image_quantize_s2d_kernel(const float* __
         }
 #pragma unroll
         for (int dx = 0; dx < 2; ++dx) {
-          const float qf = fminf(fmaxf(rintf(vals[dx] * inv), -qmax), qmax);
+          const float qf = fminf(fmaxf(rintf(scale(vals[dx])), -qmax), qmax);
           int d[L];
           split_limbs<L>((int)qf, d);
           const int g = dy * 2 + dx;  // byte 4 g + ch of the 16
@@ -174,14 +174,14 @@ __global__ __launch_bounds__(256) void maxpool_quantize_kernel(const float* __re
     const size_t o = (((size_t)img * ho + oh) * wo + ow) * c + 4 * cq;
     if (out_f32) st16(out_f32 + o, v4i{__float_as_int(m.x), __float_as_int(m.y), __float_as_int(m.z), __float_as_int(m.w)});
     const float am = absmax[img];
-    const float inv = am > 0.f ? qmax / am : 0.f;
+    const ActScale scale = act_scale<L>(am);
     const float vals[4] = {m.x, m.y, m.z, m.w};
     unsigned int word[L];
 #pragma unroll
     for (int l = 0; l < L; ++l) word[l] = 0u;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const float qf = fminf(fmaxf(rintf(vals[k] * inv), -qmax), qmax);
+      const float qf = fminf(fmaxf(rintf(scale(vals[k])), -qmax), qmax);
       int d[L];
       split_limbs<L>((int)qf, d);
 #pragma unroll
@@ -618,6 +618,7 @@ extern "C" int smpq_act_absmax(const float* x, int n, int64_t per_image, float* 
                                smpq_stream_t stream) {
   if (!x || !absmax || n <= 0 || per_image <= 0)
     return fail(SMPQ_E_INVALID, "smpq_act_absmax: bad arguments");
+  if (n > 65535) return fail(SMPQ_E_SHAPE, "smpq_act_absmax: at most 65535 images per call (one grid row each)");
   // ~4 workgroups per CU in total, few atomics per image (no contention on one address)
   int chunks = (1024 + n - 1) / n;
   const int maxc = (int)((per_image / 4 + 255) / 256);

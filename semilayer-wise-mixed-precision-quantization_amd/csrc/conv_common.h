@@ -59,6 +59,21 @@ __device__ __host__ constexpr float act_qmax() {
   return L == 1 ? 127.f : (L == 2 ? 32512.f : 8323072.f);
 }
 
+// The activation quantizers' scale for a per-image range am: code = rne((x * pre) * inv), clamped to
+// +-QMAX. pre is 1 and inv = QMAX / am, except below 2^-64, where both sides are scaled by 2^64 first:
+// QMAX / am passes FLT_MAX from am ~ 2.4e-32 at 3 limbs, and an infinite inv turns every zero
+// activation into NaN and then, through the clamp, into -QMAX. Powers of two scale exactly, so every
+// code that the unscaled form computed with a finite inv is unchanged.
+struct ActScale {
+  float pre, inv;
+  __device__ __forceinline__ float operator()(float x) const { return (x * pre) * inv; }
+};
+template <int L>
+__device__ __forceinline__ ActScale act_scale(float am) {
+  const float pre = am < 0x1p-64f ? 0x1p64f : 1.f;
+  return {pre, am > 0.f ? act_qmax<L>() / (am * pre) : 0.f};
+}
+
 // The (activation limb la, weight limb lw) passes every conv kernel keeps: those with
 // la + lw >= limb_smin(L, LW) (the products of two low digits are below the output's resolution when
 // both sides are wide); pass (la, lw) adds into int32 accumulator la + lw - SMIN of limb_nacc(L, LW),

@@ -269,10 +269,10 @@ __global__ __launch_bounds__(256) void image_quantize_c4_kernel(const float* __r
        p += (long long)gridDim.x * blockDim.x) {
     const long long img = p / hw, r = p - img * hw;
     const float am = absmax[img];
-    const float inv = am > 0.f ? qmax / am : 0.f;
+    const ActScale scale = act_scale<L>(am);
     unsigned word[L] = {0u, 0u, 0u};
     for (int ch = 0; ch < c; ++ch) {
-      const float qf = fminf(fmaxf(rintf(x[(img * c + ch) * hw + r] * inv), -qmax), qmax);
+      const float qf = fminf(fmaxf(rintf(scale(x[(img * c + ch) * hw + r])), -qmax), qmax);
       int d[L];
       split_limbs<L>((int)qf, d);
 #pragma unroll
