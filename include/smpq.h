@@ -746,8 +746,11 @@ int smpq_trial_rows_conv_restore_host(const int32_t* channels, int nrows, int li
  * A 16-output-channel fragment of the kernel covers max(1, 16 / og) groups and reads
  * S = cg * max(1, 16 / og) consecutive input channels.
  * smpq_conv2d_grouped_supported: 1 for groups >= 2, 3x3 / pad 1 / stride 1 or 2, limbs == 3,
- *   wlimbs 1 or 3, cin % 16 == 0, cout % 16 == 0, og dividing 16 or divided by 16, S one of 16, 32,
- *   64, and a halo patch of the 64-output-channel workgroup's input channels that fits LDS; else 0.
+ *   wlimbs 1 or 3, cin % 16 == 0, cout % 16 == 0, og dividing 16 or divided by 16, and either S one
+ *   of 16, 32, 64 with a halo patch of the 64-output-channel workgroup's input channels that fits LDS
+ *   (the fragment's K resident in registers), or cg >= 128 with cg % 64 == 0 and og % 64 == 0 (S = cg;
+ *   K streamed in 64-channel chunks by the wide-group kernel, which reads the same expanded copy and
+ *   not its indicator plane) and an expanded copy below 2 GiB; else 0.
  * smpq_pack_weights_grouped: the per-row arithmetic of smpq_pack_weights_ex (step, wlimbs, offset,
  *   wscale, status as there) on w [cout][cg][kh][kw] for any cg: compact codes [wlimbs][cout][kh*kw*cg],
  *   k = tap * cg + ci.

@@ -137,6 +137,29 @@ int launch_resident_chain(const ConvArgs& a, const ConvArgs* b, const ConvArgs* 
 void resident_sg_map(int block, int blocks, int nss, int* sslab, int* tile0);
 long long resident_sg_grid(long long budget, long long ntiles, int nss);
 
+// grouped 3x3 kernels: conv_grouped.hip (a fragment span of 16, 32 or 64 input channels, the fragment's
+// codes resident in registers) and conv_grouped_wide.hip (cin / groups and cout / groups multiples of
+// 64, cin / groups >= 128: K streamed in 64-channel chunks). Both read the fragment-ordered copy of
+// smpq_weights_grouped_expand.
+struct GroupedArgs {
+  const int8_t* xq;       // [3][n][h][w][cin]
+  long long plane;        // bytes per activation limb plane
+  const float* x_absmax;  // [n]
+  const int8_t* wexp;     // [planes][nfrag][NK][64][16] fragment-ordered codes (+ indicator plane)
+  const int32_t* w_off;   // [cout] or NULL
+  const float* col_scale;
+  const float* col_shift;
+  float* y;
+  float* y_absmax;
+  int8_t* yq;
+  int32_t* overflow;
+  float yq_inv, inv_qmax;
+  int n, h, w, cin, cout, ho, wo, cg, og, nfrag, relu;
+  int ntw, tiles_img, tiles;
+};
+bool grouped_wide_shape(int cg, int og);
+int launch_grouped_wide(const GroupedArgs& a, int wlimbs, int stride, bool lean, hipStream_t s);
+
 // The 4 codes (channels 0..3) held by one dword per limb plane, w[l] = the 4 balanced digits of
 // limb l: q = sum_l d_l 256^l. With u_l = d_l + 128 (byte ^ 0x80) for the low limbs,
 // q = sext24(u0 | u1 << 8 | d2 << 16) - 0x8080 (L = 3), sext16(u0 | d1 << 8) - 0x80 (L = 2).

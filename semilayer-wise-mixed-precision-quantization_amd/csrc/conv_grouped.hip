@@ -8,7 +8,8 @@
 // zero codes to NK = ceil(9 S / 64) MFMA steps; a code outside its row's own group is zero
 // (smpq_weights_grouped_expand). A lane of the MFMA holds 16 consecutive K bytes, i.e. one 16-channel
 // chunk of one tap of one pixel: chunk kk = 4 j + (lane >> 4) of step j is tap kk / (S / 16), channels
-// 16 (kk % (S / 16)) .. + 15 of the span. Built for S = 16, 32, 64.
+// 16 (kk % (S / 16)) .. + 15 of the span. Built for S = 16, 32, 64; a span S = cg >= 128 with cg and og
+// multiples of 64 goes to the K-streaming kernel of conv_grouped_wide.hip, which reads the same copy.
 //
 // Weight-stationary. One wave owns one fragment and loads its codes once, NK x 4 VGPRs per weight
 // plane, straight from the fragment-ordered copy ([plane][fragment][step][lane][16 B]: one coalesced
@@ -41,23 +42,6 @@ constexpr int kGT = 8;                // output tile edge
 constexpr int kGWaves = 4;            // fragments per workgroup
 constexpr int kGLdsMax = 160 * 1024;  // LDS per workgroup on gfx950
 constexpr long long kGBytesMax = 0x7fffff00LL;
-
-struct GroupedArgs {
-  const int8_t* xq;       // [3][n][h][w][cin]
-  long long plane;        // bytes per activation limb plane
-  const float* x_absmax;  // [n]
-  const int8_t* wexp;     // [planes][nfrag][NK][64][16] fragment-ordered codes (+ indicator plane)
-  const int32_t* w_off;   // [cout] or NULL
-  const float* col_scale;
-  const float* col_shift;
-  float* y;
-  float* y_absmax;
-  int8_t* yq;
-  int32_t* overflow;
-  float yq_inv, inv_qmax;
-  int n, h, w, cin, cout, ho, wo, cg, og, nfrag, relu;
-  int ntw, tiles_img, tiles;
-};
 
 __host__ __device__ inline int grouped_span(int f, int cg, int og) { return (16 * f / og) * cg; }
 inline int grouped_S(int cg, int og) { return cg * (og >= 16 ? 1 : 16 / og); }
@@ -336,6 +320,10 @@ __global__ void grouped_expand_kernel(const int8_t* __restrict__ codes, int wlim
   out[i] = (int8_t)v;
 }
 
+long long grouped_expand_bytes(int wlimbs, int cout, int cg, int og) {
+  return (long long)(wlimbs + (wlimbs == 1 ? 1 : 0)) * (cout / 16) * grouped_nk(grouped_S(cg, og) / 16) * 1024;
+}
+
 bool grouped_supported(int cin, int cout, int groups, int kh, int kw, int stride, int pad, int limbs, int wlimbs) {
   if (groups < 2 || cin <= 0 || cout <= 0 || cin % groups != 0 || cout % groups != 0) return false;
   if (kh != 3 || kw != 3 || pad != 1 || (stride != 1 && stride != 2)) return false;
@@ -344,12 +332,11 @@ bool grouped_supported(int cin, int cout, int groups, int kh, int kw, int stride
   const int cg = cin / groups, og = cout / groups;
   if (!(og <= 16 ? 16 % og == 0 : og % 16 == 0)) return false;
   const int S = grouped_S(cg, og);
+  // conv_grouped_wide.hip: whole 64-channel K chunks, a workgroup's 64 channels inside one group; the
+  // expanded copy within its 32-bit buffer offsets
+  if (grouped_wide_shape(cg, og)) return grouped_expand_bytes(wlimbs, cout, cg, og) <= kGBytesMax;
   if (S != 16 && S != 32 && S != 64) return false;
   return grouped_lds_bytes(cout / 16, cg, og, S, stride) <= kGLdsMax;
-}
-
-long long grouped_expand_bytes(int wlimbs, int cout, int cg, int og) {
-  return (long long)(wlimbs + (wlimbs == 1 ? 1 : 0)) * (cout / 16) * grouped_nk(grouped_S(cg, og) / 16) * 1024;
 }
 
 }  // namespace
@@ -399,7 +386,8 @@ extern "C" int smpq_conv2d_grouped_fwd_q(const int8_t* xq, const float* x_absmax
   if (!grouped_supported(cin, cout, groups, kh, kw, stride, pad, limbs, wlimbs))
     return fail(SMPQ_E_SHAPE, "smpq_conv2d_grouped_fwd_q: unsupported geometry (smpq_conv2d_grouped_supported: 3x3 / "
                               "pad 1 / stride 1 or 2, groups >= 2, cin % 16 == 0, cout % 16 == 0, cout / groups "
-                              "dividing or divided by 16, a fragment span of 16, 32 or 64 channels)");
+                              "dividing or divided by 16, a fragment span of 16, 32 or 64 channels, or cin / groups "
+                              ">= 128 with cin / groups and cout / groups multiples of 64)");
   if ((((uintptr_t)xq | (uintptr_t)codes_expanded | (uintptr_t)col_scale | (uintptr_t)col_shift | (uintptr_t)offset |
         (uintptr_t)y | (uintptr_t)yq) & 15) != 0)
     return fail(SMPQ_E_INVALID, "smpq_conv2d_grouped_fwd_q: operands must be 16-B aligned");
@@ -429,10 +417,11 @@ extern "C" int smpq_conv2d_grouped_fwd_q(const int8_t* xq, const float* x_absmax
   a.tiles_img = ((a.ho + kGT - 1) / kGT) * a.ntw;
   if ((long long)n * a.tiles_img > 0x7fffffffLL) return fail(SMPQ_E_SHAPE, "smpq_conv2d_grouped_fwd_q: too many tiles");
   a.tiles = n * a.tiles_img;
-  const int S = grouped_S(a.cg, a.og);
-  const int lds_bytes = grouped_lds_bytes(a.nfrag, a.cg, a.og, S, stride);
   const bool lean = yq && !y && !y_absmax;
   hipStream_t s = (hipStream_t)stream;
+  if (grouped_wide_shape(a.cg, a.og)) return launch_grouped_wide(a, wlimbs, stride, lean, s);
+  const int S = grouped_S(a.cg, a.og);
+  const int lds_bytes = grouped_lds_bytes(a.nfrag, a.cg, a.og, S, stride);
   if (wlimbs == 3) return launch_grouped_w<3, false>(a, S / 16, stride, lean, lds_bytes, s);
   return a.w_off ? launch_grouped_w<1, true>(a, S / 16, stride, lean, lds_bytes, s)
                  : launch_grouped_w<1, false>(a, S / 16, stride, lean, lds_bytes, s);

@@ -17,7 +17,8 @@ downsample convs, mid-search semilayers) have no integer code; they run on the s
 with their fp32 weights in per-channel fixed point with as many int8 limbs as the activations
 (16 or 24 bits), counted in ``smpq.stats["fixed_conv"]``. The 7x7/2/3 stem on <= 4 channels runs
 as a 4x4 conv over space-to-depth pixels on the same kernel. A grouped 3x3 conv (ResNeXt) runs on
-the block-diagonal kernel of csrc/conv_grouped.hip, a dense 3x3 conv with padding = dilation 2, 4 or
+the block-diagonal kernel of csrc/conv_grouped.hip (or, with cin / groups >= 128 and both per-group widths
+multiples of 64, the K-streaming kernel of csrc/conv_grouped_wide.hip), a dense 3x3 conv with padding = dilation 2, 4 or
 8 (replace_stride_with_dilation) on the phase-lattice kernel of csrc/conv_dilated.hip, a dense 3x3 / pad
 1 / stride 1 or 2 or 1x1 / stride 1 conv with cin % 16 == 0 but cin % 64 != 0 (width_per_group != 64) on
 the channel-slab kernel of csrc/conv_narrow.hip, the 3x3 / stride 1 / pad 1 stem on <= 4 channels of a
