@@ -842,6 +842,33 @@ int smpq_conv2d_narrow_fwd_q(const int8_t* xq, const float* x_absmax, int n, int
                              float* y_absmax, int8_t* yq, float yq_range, int32_t* overflow,
                              const int8_t* residual_q, float residual_range, smpq_stream_t stream);
 
+/* ---- dilated narrow-channel 3x3 conv (additions to ABI 7) -----------------------------------------
+ * The conv2 of a Bottleneck built with width_per_group != 64 and replace_stride_with_dilation: dense
+ * (groups 1), 3x3, stride 1, padding == dilation == d, cin % 16 == 0 but cin % 64 != 0
+ * (csrc/conv_narrow_dilated.hip): the d * d phase lattices of the dilated kernel, each run as the
+ * narrow kernel runs a 3x3 / pad 1 / stride 1 conv.
+ * smpq_conv2d_narrow_dilated_supported: 1 exactly for 3x3, stride 1, pad == dilation in {2, 4, 8},
+ *   cin % 16 == 0, cin % 64 != 0, cout % 16 == 0, limbs == 3, wlimbs 1 or 3; else 0. The answers of
+ *   smpq_conv2d_dilated_supported and smpq_conv2d_narrow_supported are what they were.
+ * smpq_conv2d_narrow_dilated_fwd_q: smpq_conv2d_dilated_fwd_q on the weight operand of
+ *   smpq_conv2d_narrow_fwd_q: codes the compact codes [wlimbs][cout][9 cin] of
+ *   smpq_pack_weights_grouped with cg = cin, codes_expanded their copy by
+ *   smpq_weights_narrow_expand(codes, wlimbs, cout, cin, 3, 3, 1, ...) (the stride-1 copy: a phase
+ *   lattice is a stride-1 conv), which the kernel reads. y = relu?(conv_real * col_scale[c] +
+ *   col_shift[c]) as fp32 NHWC y and / or limb planes yq at the static yq_range with the overflow flag;
+ *   y_absmax optional; no residual. All three activation planes together, and each output tensor, stay
+ *   below 2 GiB (SMPQ_E_SHAPE otherwise: split the batch). SMPQ_E_SHAPE for a geometry
+ *   smpq_conv2d_narrow_dilated_supported refuses, SMPQ_E_INVALID for null or misaligned (16 B) pointers
+ *   or other limb counts, before any launch. */
+int smpq_conv2d_narrow_dilated_supported(int cin, int cout, int kh, int kw, int stride, int pad, int dilation,
+                                         int limbs, int wlimbs);
+int smpq_conv2d_narrow_dilated_fwd_q(const int8_t* xq, const float* x_absmax, int n, int h, int w, int cin,
+                                     const int8_t* codes, const int8_t* codes_expanded, int wlimbs,
+                                     const int32_t* offset, int cout, int kh, int kw, int stride, int pad,
+                                     int dilation, const float* col_scale, const float* col_shift, int relu,
+                                     int limbs, float* y, float* y_absmax, int8_t* yq, float yq_range,
+                                     int32_t* overflow, smpq_stream_t stream);
+
 /* ---- 3x3 small-channel stem (additions to ABI 7) -------------------------------------------------
  * The conv1 of a CIFAR-style ResNet: dense 3x3 / stride 1 / pad 1 on cin <= 4 image channels
  * (csrc/conv_stem3.hip). K = 9 taps x 4 channels = 36 bytes, one v_mfma_i32_16x16x64_i8 step.

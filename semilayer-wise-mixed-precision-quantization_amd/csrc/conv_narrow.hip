@@ -37,27 +37,17 @@
 // lean_quad, encode4, decode4), so a value is rounded as the dense kernels round it, with the residual
 // as fp32 NHWC (general form) or as limb planes + range (both forms). Every global access of a tensor
 // goes through a range-checked buffer resource with 32-bit offsets.
-#include <map>
-#include <mutex>
-#include <tuple>
-
 #include "lds_dma.h"
 
 namespace smpq {
 namespace {
 
-constexpr int kNT = 8;                // output tile edge
-constexpr int kNWaves = 4;            // fragments per workgroup
-constexpr int kNLdsMax = 160 * 1024;  // LDS per workgroup on gfx950
+// (the slab geometry, the fragment-read offsets and the K step are in conv_common.h: conv_narrow_dilated.hip
+// runs its phase lattices on them)
+constexpr int kNT = kNarrowTile;         // output tile edge
+constexpr int kNWaves = 4;               // fragments per workgroup
+constexpr int kNLdsMax = kNarrowLdsMax;  // LDS per workgroup on gfx950
 constexpr long long kNBytesMax = 0x7fffff00LL;
-
-struct NarrowGeo {
-  int taps, pw;        // 9 or 1; patch edge in pixels
-  int cs, nslab, cl;   // chunks per slab, slabs, chunks of the last slab
-  int pp, rp;          // pixel and patch-row pitch in 16-B chunks
-  int nkf, nk;         // MFMA steps of a full slab, of all slabs
-  int lds_bytes;
-};
 
 struct NarrowArgs {
   const int8_t* xq;       // [3][n][h][w][cin]
@@ -81,130 +71,16 @@ struct NarrowArgs {
   NarrowGeo g;
 };
 
-// ds_read_b128 lane groups of gfx950 (tools/halo_conflicts.py): each is served in one pass when its 16
-// addresses fall in 16 different 16-B slots mod 256 B
-constexpr int kLaneGroups[2][16] = {{0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27},
-                                    {4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31}};
-
-// chunk offset (16 B units) of a lane's fragment read: pixel fragment pf, K step j
-__host__ __device__ inline int narrow_pix(int frow, int pf, int stride, int pp, int rp) {
-  return stride * (2 * pf + (frow >> 3)) * rp + stride * (frow & 7) * pp;
-}
-__host__ __device__ inline int narrow_tap(int kk, int cwc, int taps, int pp, int rp) {
-  const int tap = kk / cwc, sub = kk - tap * cwc;
-  return tap < taps ? (tap / 3) * rp + (tap % 3) * pp + sub : 0;  // K padding: the codes are zero
-}
-
-// worst extra LDS cycles of one fragment read over all steps, pixel fragments and lane groups
-int narrow_conflicts(int cwc, int taps, int stride, int pp, int rp) {
-  int worst = 0;
-  for (int j = 0; j < (taps * cwc + 3) / 4; ++j)
-    for (int pf = 0; pf < 4; ++pf)
-      for (int half = 0; half < 2; ++half)
-        for (int g = 0; g < 2; ++g) {
-          int chunk[16];
-          for (int i = 0; i < 16; ++i) {
-            const int lane = kLaneGroups[g][i] + 32 * half;
-            chunk[i] = narrow_pix(lane & 15, pf, stride, pp, rp) + narrow_tap(4 * j + (lane >> 4), cwc, taps, pp, rp);
-          }
-          for (int b = 0; b < 16; ++b) {
-            int distinct = 0;  // different chunks in bank slot b
-            for (int q = 0; q < 16; ++q) {
-              bool fresh = (chunk[q] & 15) == b;
-              for (int r = 0; r < q; ++r) fresh = fresh && chunk[r] != chunk[q];
-              distinct += fresh ? 1 : 0;
-            }
-            worst = distinct - 1 > worst ? distinct - 1 : worst;
-          }
-        }
-  return worst;
-}
-
-inline int narrow_patch_bytes(int pw, int rp) { return (3 * pw * rp * 16 + 1023) / 1024 * 1024; }
-
-// pitches of a slab of cwc chunks: of pixel pitches cwc .. cwc + 2 and up to 15 chunks of row padding,
-// the pair with the fewest conflicts, then the smallest image; false when none fits LDS
-bool narrow_pitch(int cwc, int taps, int stride, int pw, int& pp, int& rp) {
-  int best = 1 << 30;
-  for (int p = cwc; p < cwc + 3; ++p)
-    for (int r = pw * p; r < pw * p + 16; ++r) {
-      if (narrow_patch_bytes(pw, r) > kNLdsMax) break;
-      const int score = narrow_conflicts(cwc, taps, stride, p, r) * 65536 + r;
-      if (score < best) best = score, pp = p, rp = r;
-    }
-  return best != (1 << 30);
-}
-
 bool narrow_shape_ok(int cin, int cout, int kh, int kw, int stride, int pad) {
   if (cin <= 0 || cout <= 0 || cin % 16 != 0 || cin % 64 == 0 || cout % 16 != 0) return false;
   if (kh == 3 && kw == 3) return pad == 1 && (stride == 1 || stride == 2);
   return kh == 1 && kw == 1 && pad == 0 && stride == 1;
 }
 
-// the slab walk, the LDS image and the step counts of a supported shape (cached: the pitch search
-// enumerates every fragment read)
-bool narrow_geo(int cin, int kh, int stride, NarrowGeo& g) {
-  static std::mutex mu;
-  static std::map<std::tuple<int, int, int>, NarrowGeo> cache;
-  std::lock_guard<std::mutex> lock(mu);
-  const auto key = std::make_tuple(cin, kh, stride);
-  const auto it = cache.find(key);
-  if (it != cache.end()) {
-    g = it->second;
-    return g.cs > 0;
-  }
-  g = NarrowGeo{};
-  g.taps = kh * kh;
-  g.pw = kh == 1 ? kNT : stride * (kNT - 1) + 3;
-  const int cc = cin / 16;
-  for (int cwc = cc; cwc >= 1 && g.cs == 0; --cwc)
-    if (narrow_patch_bytes(g.pw, g.pw * cwc) <= kNLdsMax && narrow_pitch(cwc, g.taps, stride, g.pw, g.pp, g.rp))
-      g.cs = cwc;
-  if (g.cs > 0) {
-    g.nslab = (cc + g.cs - 1) / g.cs;
-    g.cl = cc - (g.nslab - 1) * g.cs;
-    g.nkf = (g.taps * g.cs + 3) / 4;
-    g.nk = (g.nslab - 1) * g.nkf + (g.taps * g.cl + 3) / 4;
-    g.lds_bytes = narrow_patch_bytes(g.pw, g.rp);
-  }
-  cache[key] = g;
-  return g.cs > 0;
-}
-
 bool narrow_supported(int cin, int cout, int kh, int kw, int stride, int pad, int limbs, int wlimbs) {
   if (limbs != 3 || (wlimbs != 1 && wlimbs != 3) || !narrow_shape_ok(cin, cout, kh, kw, stride, pad)) return false;
   NarrowGeo g;
   return narrow_geo(cin, kh, stride, g);
-}
-
-long long narrow_expand_bytes(int wlimbs, int cout, const NarrowGeo& g) {
-  return (long long)(wlimbs + (wlimbs == 1 ? 1 : 0)) * (cout / 16) * g.nk * 1024;
-}
-
-// the resident form's step count, or 0 for the streaming form
-int narrow_resident_steps(const NarrowGeo& g) {
-  return g.nslab == 1 && (g.nk == 1 || g.nk == 2 || g.nk == 3 || g.nk == 5 || g.nk == 7) ? g.nk : 0;
-}
-
-// one K step of the four pixel fragments: the lane's chunk at toff of the staged patch against the
-// step's codes w[0 .. LW) (and the all-ones plane w[LW])
-template <int LW, bool OFF, int NACC, int SMIN>
-__device__ __forceinline__ void narrow_step(const int8_t* lds, int plimb, const int (&pixoff)[4], int toff,
-                                            const v4i* w, v4i (&acc)[NACC][4], v4i (&gs)[OFF ? 3 : 1][4]) {
-#pragma unroll
-  for (int pf = 0; pf < 4; ++pf) {
-    v4i fb[3];
-#pragma unroll
-    for (int l = 0; l < 3; ++l) fb[l] = *reinterpret_cast<const v4i*>(lds + l * plimb + pixoff[pf] + toff);
-#pragma unroll
-    for (int la = 0; la < 3; ++la) {
-#pragma unroll
-      for (int lw = 0; lw < LW; ++lw)
-        if (la + lw >= SMIN)
-          acc[la + lw - SMIN][pf] = __builtin_amdgcn_mfma_i32_16x16x64_i8(w[lw], fb[la], acc[la + lw - SMIN][pf], 0, 0, 0);
-      if constexpr (OFF) gs[la][pf] = __builtin_amdgcn_mfma_i32_16x16x64_i8(w[LW], fb[la], gs[la][pf], 0, 0, 0);
-    }
-  }
 }
 
 // LW weight limbs (1 or 3), OFF: weight offsets (LW == 1), LEAN: the static-range limb-plane

@@ -133,6 +133,9 @@ _PROTOS = {
     "smpq_weights_narrow_expand": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "smpq_conv2d_narrow_fwd_q": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp,
                                       _i, _i, _vp, _vp, _vp, ctypes.c_float, _vp, _vp, ctypes.c_float, _vp]),
+    "smpq_conv2d_narrow_dilated_supported": (_i, [_i] * 9),
+    "smpq_conv2d_narrow_dilated_fwd_q": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp,
+                                              _vp, _i, _i, _vp, _vp, _vp, ctypes.c_float, _vp, _vp]),
     "smpq_stem3_supported": (_i, [_i] * 8),
     "smpq_image_quantize_c4": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "smpq_stem_conv3_q": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp,

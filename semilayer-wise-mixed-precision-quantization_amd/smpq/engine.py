@@ -240,8 +240,9 @@ def run_conv(conv, bn, act, relu, residual=None, want_amax=True, ctx=None, want_
             special = functools.partial(ops.conv2d_grouped_q, act.limbs(), act.amax, codes, offset, conv.stride[0],
                                         col_scale, col_shift)
         elif conv.dilation[0] != 1:
-            special = functools.partial(ops.conv2d_dilated_q, act.limbs(), act.amax, codes, offset, conv.dilation[0],
-                                        col_scale, col_shift)
+            # (on cin % 64 != 0 the dilated narrow-channel kernel, which reads the narrow kernel's operand)
+            special = functools.partial(ops.conv2d_narrow_dilated_q if conv.narrow_dilated() else ops.conv2d_dilated_q,
+                                        act.limbs(), act.amax, codes, offset, conv.dilation[0], col_scale, col_shift)
         if special is not None and (residual is not None or res_q is not None):
             raise RuntimeError("smpq: residual on a grouped or dilated conv")
         if special is None and conv.narrow():

@@ -1067,6 +1067,80 @@ def conv2d_narrow_q(xq, x_absmax, codes, offset, col_scale, col_shift, residual=
     return out
 
 
+# ---- dilated narrow-channel 3x3 conv (include/smpq.h: the conv2 of a Bottleneck with width_per_group != 64 and
+# replace_stride_with_dilation). No switch of its own: SMPQ_NARROW=0 or SMPQ_DILATED=0 puts these convs back on torch
+def conv_narrow_dilated_supported(cin, cout, kh, kw, stride, pad, dilation, limbs=None, wlimbs=3):
+    """Does smpq_conv2d_narrow_dilated_fwd_q take this geometry (and are both the SMPQ_NARROW and the SMPQ_DILATED
+    switch on)?"""
+    limbs = get_act_limbs() if limbs is None else limbs
+    return NARROW[0] and DILATED[0] and bool(_lib.load().smpq_conv2d_narrow_dilated_supported(
+        int(cin), int(cout), int(kh), int(kw), int(stride), int(pad), int(dilation), int(limbs), int(wlimbs)))
+
+
+def conv2d_narrow_dilated_q(xq, x_absmax, codes, offset, dilation, col_scale, col_shift, relu=False, y_absmax=None,
+                            out=None, emit_range=None, overflow=None, want_f32=True):
+    """Dense 3x3 / stride 1 conv with padding = dilation (2, 4 or 8) on int8 limb planes xq [3, n, h, w, cin],
+    cin % 16 == 0 and cin % 64 != 0, with the codes of pack_weights_narrow(w, step, wlimbs, 1) (a phase lattice is
+    a stride-1 conv): y = conv(x, w) * s_x * col_scale + col_shift (relu), NHWC fp32; with ``emit_range`` also
+    (or, with want_f32=False, only) the output's limb planes [3, n, h, w, cout], returned as (y or None, yq), with
+    ``overflow`` set when a value exceeded the range. No residual. A batch whose tensors would reach 2 GiB runs in
+    image chunks."""
+    _req(xq.is_cuda and xq.dtype == torch.int8 and xq.dim() == 5 and xq.is_contiguous(),
+         "narrow dilated conv: xq must be [L,n,h,w,c] int8")
+    limbs, n, h, w, cin = xq.shape
+    expanded, geo = getattr(codes, "_smpq_nx", None), getattr(codes, "_smpq_narrow", None)
+    _req(expanded is not None and geo == (3, 1) and codes.dim() == 3,
+         "narrow dilated conv: codes of pack_weights_narrow(w, step, wlimbs, 1) on a 3x3 weight")
+    wlimbs, cout, K = codes.shape
+    _req(K == 9 * cin and codes.dtype == torch.int8 and codes.is_contiguous() and codes.device == xq.device
+         and expanded.device == xq.device, "narrow dilated conv: codes shape")
+    _req(conv_narrow_dilated_supported(cin, cout, 3, 3, 1, dilation, dilation, limbs, wlimbs),
+         "narrow dilated conv: unsupported geometry or limb counts (conv_narrow_dilated_supported)")
+    _req(offset is None or (offset.dtype == torch.int32 and offset.numel() == cout and wlimbs == 1),
+         "narrow dilated conv: offset")
+    _req(x_absmax.dtype == torch.float32 and x_absmax.numel() == n, "narrow dilated conv: x_absmax")
+    for t in (col_scale, col_shift):
+        _req(t.dtype == torch.float32 and t.numel() == cout and t.is_contiguous() and t.device == xq.device,
+             "narrow dilated conv: col vectors")
+    yq = None
+    if emit_range is not None:
+        _req(emit_range > 0, "narrow dilated conv: emit_range must be > 0")
+        _req(overflow is not None and overflow.dtype == torch.int32 and overflow.device == xq.device,
+             "narrow dilated conv: overflow")
+        yq = torch.empty(limbs, n, h, w, cout, dtype=torch.int8, device=xq.device)
+    else:
+        want_f32 = True
+    if out is None and want_f32:
+        out = torch.empty(n, h, w, cout, dtype=torch.float32, device=xq.device)
+    _req(out is None or (out.shape == (n, h, w, cout) and out.is_contiguous()), "narrow dilated conv: out shape")
+    if y_absmax is not None:
+        _req(y_absmax.numel() == n and y_absmax.dtype == torch.float32, "narrow dilated conv: y_absmax")
+    # the kernel's 32-bit offsets run over all three limb planes of a tensor
+    per_img = max(limbs * h * w * cin, (limbs if yq is not None else 0) * h * w * cout,
+                  (4 if out is not None else 0) * h * w * cout)
+    chunks = _image_chunks(n, per_img, "narrow dilated conv")
+    if chunks:
+        for i0, i1 in chunks:
+            r = conv2d_narrow_dilated_q(xq[:, i0:i1].contiguous(), x_absmax[i0:i1], codes, offset, dilation, col_scale,
+                                        col_shift, relu=relu, y_absmax=None if y_absmax is None else y_absmax[i0:i1],
+                                        out=None if out is None else out[i0:i1], emit_range=emit_range,
+                                        overflow=overflow, want_f32=want_f32)
+            if yq is not None:
+                yq[:, i0:i1].copy_(r[1])
+        return (out, yq) if emit_range is not None else out
+    hook = _CONV_HOOK[0]
+    if hook is not None:
+        hook.begin()
+    _launch(xq.device, "smpq_conv2d_narrow_dilated_fwd_q", xq, x_absmax, n, h, w, cin, codes, expanded, int(wlimbs),
+            offset, cout, 3, 3, 1, int(dilation), int(dilation), col_scale, col_shift, 1 if relu else 0, int(limbs), out,
+            y_absmax, yq, float(emit_range or 0.0), overflow)
+    if hook is not None:
+        hook.end(alg_work(n, h, w, cin, cout, 3, 3, h, w, limbs, wlimbs, out is not None, yq is not None, False, False))
+    if emit_range is not None:
+        return out, yq
+    return out
+
+
 # ---- 3x3 small-channel stem (include/smpq.h: the conv1 of a CIFAR-style ResNet) ----------------------
 # SMPQ_STEM3=0 puts the 3x3 / stride 1 stem on <= 4 channels back on torch (QConv2d.c4_stem then refuses it)
 STEM3 = [os.environ.get("SMPQ_STEM3", "1") != "0"]

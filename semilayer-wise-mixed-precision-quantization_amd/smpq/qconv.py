@@ -21,10 +21,11 @@ the block-diagonal kernel of csrc/conv_grouped.hip (or, with cin / groups >= 128
 multiples of 64, the K-streaming kernel of csrc/conv_grouped_wide.hip), a dense 3x3 conv with padding = dilation 2, 4 or
 8 (replace_stride_with_dilation) on the phase-lattice kernel of csrc/conv_dilated.hip, a dense 3x3 / pad
 1 / stride 1 or 2 or 1x1 / stride 1 conv with cin % 16 == 0 but cin % 64 != 0 (width_per_group != 64) on
-the channel-slab kernel of csrc/conv_narrow.hip, the 3x3 / stride 1 / pad 1 stem on <= 4 channels of a
+the channel-slab kernel of csrc/conv_narrow.hip, such a 3x3 / stride 1 conv with padding = dilation 2, 4 or 8 (both at
+once) on the phase-lattice channel-slab kernel of csrc/conv_narrow_dilated.hip, the 3x3 / stride 1 / pad 1 stem on <= 4 channels of a
 small-image (CIFAR-style) ResNet, with cout % 64 == 0 and 3 activation limbs, on the one-step kernel of
 csrc/conv_stem3.hip (``c4_stem`` / ``packed_c4``, like the 7x7 stem outside ``packed()``). Only geometries the kernels do not cover (other grouped
-convs, other dilations, grouped + dilated, grouped or dilated narrow convs, cin % 16 != 0, other kernel
+convs, other dilations, grouped + dilated, grouped narrow convs, cin % 16 != 0, other kernel
 sizes or strides on cin % 64 != 0, cout % 16 != 0) fall back to
 ``F.conv2d`` on the GPU (counted in ``stats["fp32_conv"]``).
 """
@@ -161,11 +162,12 @@ class QConv2d(nn.Conv2d):
               and self.padding_mode == "zeros" and self.stride[0] == self.stride[1]
               and self.padding[0] == self.padding[1])
         if ok and self.dilation[0] != 1:
-            # the dilated 3x3 kernel (ops.conv2d_dilated_q): dense only, both weight forms packed() can produce
+            # the dilated 3x3 kernels (ops.conv2d_dilated_q, or ops.conv2d_narrow_dilated_q on cin % 64 != 0): dense
+            # only, both weight forms packed() can produce
+            rule = ops.conv_narrow_dilated_supported if self.in_channels % 64 != 0 else ops.conv_dilated_supported
             return self.groups == 1 and all(
-                ops.conv_dilated_supported(self.in_channels, self.out_channels, self.kernel_size[0],
-                                           self.kernel_size[1], self.stride[0], self.padding[0], self.dilation[0],
-                                           wlimbs=lw) for lw in (1, 3))
+                rule(self.in_channels, self.out_channels, self.kernel_size[0], self.kernel_size[1], self.stride[0],
+                     self.padding[0], self.dilation[0], wlimbs=lw) for lw in (1, 3))
         if ok and self.groups != 1:
             # the grouped 3x3 kernel (ops.conv2d_grouped_q): both weight forms packed() can produce
             return all(ops.conv_grouped_supported(self.in_channels, self.out_channels, self.groups,
@@ -182,6 +184,10 @@ class QConv2d(nn.Conv2d):
     def narrow(self):
         """A dense conv on cin % 64 != 0 (the narrow-channel kernel's, when hip_supported())?"""
         return self.groups == 1 and self.dilation[0] == 1 and self.in_channels % 64 != 0
+
+    def narrow_dilated(self):
+        """A dense dilated conv on cin % 64 != 0 (the dilated narrow-channel kernel's, when hip_supported())?"""
+        return self.groups == 1 and self.dilation[0] != 1 and self.in_channels % 64 != 0
 
     def packed(self):
         """Weight operand of the HIP conv: (codes int8 [LW, cout, K], LW, offset | None,
@@ -207,6 +213,10 @@ class QConv2d(nn.Conv2d):
             # compact codes + the kernel's fragment-ordered copy (ops.pack_weights_narrow)
             def pack(w, step, lw):
                 return ops.pack_weights_narrow(w, step, lw, self.stride[0])
+        elif self.narrow_dilated():
+            # the same operand at stride 1: a phase lattice of the dilated conv is a 3x3 / pad 1 / stride 1 conv
+            def pack(w, step, lw):
+                return ops.pack_weights_narrow(w, step, lw, 1)
         else:
             pack = ops.pack_weights_ex
         with torch.no_grad():
@@ -328,7 +338,8 @@ class QConv2d(nn.Conv2d):
         if self.groups != 1:
             y = ops.conv2d_grouped_q(xq, amax, codes, offset, self.stride[0], wscale.contiguous(), shift)
         elif self.dilation[0] != 1:
-            y = ops.conv2d_dilated_q(xq, amax, codes, offset, self.dilation[0], wscale.contiguous(), shift)
+            fn = ops.conv2d_narrow_dilated_q if self.narrow_dilated() else ops.conv2d_dilated_q
+            y = fn(xq, amax, codes, offset, self.dilation[0], wscale.contiguous(), shift)
         elif self.narrow():
             y = ops.conv2d_narrow_q(xq, amax, codes, offset, wscale.contiguous(), shift)
         else:
